@@ -12,23 +12,37 @@ per-task alpha, weighted loss — synthetic transitions, random-init
 weights.  Compute dtype defaults to bf16 (fp32 master weights, bf16 GEMM
 mirrors) — the precision BASELINE.json's config list names for the MI355X
 learner ("8 CPU rollout workers + 1 MI355X learner bf16"); the reference
-itself is fp32-only, so the fp32 rate is measured and reported alongside
-(``fp32_value``) and available via ``--dtype fp32``.  Each timed step is
+itself is fp32-only, so ``--full`` measures the fp32 rate alongside
+(``fp32_value``); it is also available via ``--dtype fp32``.  Each timed step is
 ONE full SAC gradient update (TD target, critic fwd+bwd+Adam, actor
 fwd+bwd+Adam, alpha fwd+bwd+Adam, Polyak) — nothing is skipped or cached.
 For N>1 the learner is data-parallel: flat-bucket RCCL all-reduce of
 critic/actor/alpha gradients per update (weak scaling: per-GPU batch
 fixed).
 
-Timing: the K-step window (barrier + synchronize on both sides, MAX over
-ranks) is repeated until the cumulative timed region reaches
-``--min-timed-seconds`` (default 2 s), and the MEDIAN window is reported —
-so a small --steps can never decide the headline from a 10 ms window.
+Timing: one K-step window (barrier + synchronize on both sides, MAX over
+ranks).  A plain run times exactly that one window — ``--steps`` IS the
+number of timed steps — and does nothing else: set up, warm up, time,
+optionally ``--dump-outputs``, print the result line.  Under ``--full`` the
+window is repeated until the cumulative timed region reaches
+``--min-timed-seconds`` (default 2 s) and the MEDIAN window is reported,
+and the auxiliary measurements run too: the fp32 rate (``fp32_value``) and
+`env_steps_per_sec` (untimed region) = synthetic-env rollout throughput of
+one vectorized player with batched policy inference.
 ``ms_per_step`` × ``steps`` is always one real contiguous window.
 
-`value` = aggregate grad-steps/sec = N * K / max-over-ranks(median window).
-`env_steps_per_sec` (auxiliary, untimed region) = synthetic-env rollout
-throughput of one vectorized player with batched policy inference.
+`value` = aggregate grad-steps/sec = N * K / max-over-ranks(window).
+
+``--dump-outputs DIR`` writes, after the first timed window (exactly
+warmup + K updates from the seeded start, so two builds can be compared
+array for array), what the last timed update gave its caller: the metric
+tensors it returned (critic/actor/alpha loss, entropy) and the flat
+parameter groups it updated in place, as ``DIR/<name>.npy`` (float32,
+~7 MB for MT10-MTSAC).  Seeds fix every input (weights, replay contents,
+sampled indices, gaussian draws), and no reduction in the flagship update
+depends on execution order (pinned by
+tests/test_gpu_kernels.py::test_flagship_update_repeats_bit_for_bit), so
+two runs of one build with the same arguments write the same files.
 
 ``--async`` benches the real asynchronous topology instead (players ->
 shm rings -> learner with ingest/publish on the update path), reporting
@@ -55,17 +69,28 @@ def parse_args():
     p.add_argument("--config", type=str, default="mtsac",
                    choices=["mtsac", "sac", "vsac", "care", "mt1_care"])
     p.add_argument("--device", type=str, default=None)
-    p.add_argument("--skip-rollout-probe", action="store_true")
+    p.add_argument("--skip-rollout-probe", action="store_true",
+                   help="with --full: skip the rollout-throughput probe")
     p.add_argument("--no-graph", action="store_true",
                    help="disable hipGraph capture of the update step")
     p.add_argument("--dtype", choices=["fp32", "bf16"], default="bf16",
                    help="GEMM compute dtype (fp32 masters either way)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the auxiliary measurements (repeated "
+                        "windows with a median headline, fp32 rate, "
+                        "rollout probe); a plain run times one window only")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="write what the last update of the first timed "
+                        "window returned (metrics + updated parameter "
+                        "groups) as DIR/<name>.npy")
     p.add_argument("--min-timed-seconds", type=float, default=2.0,
-                   help="repeat the K-step window until this much total "
-                        "timed region accumulated (median window reported)")
+                   help="with --full: repeat the K-step window until this "
+                        "much total timed region accumulated (median "
+                        "window reported)")
     p.add_argument("--max-windows", type=int, default=64)
     p.add_argument("--skip-fp32-probe", action="store_true",
-                   help="skip the auxiliary fp32-rate measurement")
+                   help="with --full: skip the auxiliary fp32-rate "
+                        "measurement")
     p.add_argument("--async", dest="async_mode", action="store_true",
                    help="bench the real async topology: players -> shm "
                         "rings -> learner (single rank)")
@@ -80,7 +105,10 @@ def parse_args():
                    help="initialize the process group + run the DP code "
                         "path even at world_size 1 (single-GPU RCCL "
                         "validation / launch-gap profiling)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 def prefill_replay(replay, cfg, per_shard: int, device, seed: int):
@@ -141,11 +169,28 @@ def build_engine_and_replay(cfg, device, precision, rank, ddp=None,
     return engine, replay
 
 
+def dump_outputs(out_dir, engine, metrics):
+    """Write what the caller of the timed update receives — the metric
+    tensors it returns and the parameter groups it updated in place — as
+    float32 ``<name>.npy`` files (MT10-MTSAC: ~7 MB in all)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {f"metric_{k}": v for k, v in metrics.items()}
+    for name, group in sorted(vars(engine).items()):
+        if name.endswith("_group") and hasattr(group, "flat_data"):
+            arrays[f"params_{name}"] = group.flat_data
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32).numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.atleast_1d(a))
+
+
 def measure(engine, replay, cfg, args, device, ddp, rank,
-            label: str = "main"):
-    """Warmup, then repeat the exactly-K-step timed window (barrier + sync
-    brackets, max over ranks) until >= min-timed-seconds accumulated;
-    return (median_window_s, n_windows, graphed)."""
+            label: str = "main", dump_dir=None):
+    """Warmup, then time the exactly-K-step window (barrier + sync
+    brackets, max over ranks): once in a plain run, under --full repeated
+    until >= min-timed-seconds accumulated; return (median_window_s,
+    n_windows, graphed).  ``dump_dir``: write the outputs of the first
+    window's last update there."""
 
     def sync():
         if device.startswith("cuda"):
@@ -179,13 +224,13 @@ def measure(engine, replay, cfg, args, device, ddp, rank,
 
     def one_step():   # one GRAD UPDATE (chunked replay runs chunk of them)
         if graphed:
-            engine.graphed_update()
-        elif dp_graphed:
-            engine.dp_graphed_update()
-        else:
-            engine.update_tensors(replay.sample(cfg.batch_size,
-                                                graph_safe=True))
-            engine.update_iteration += 1
+            return engine.graphed_update()
+        if dp_graphed:
+            return engine.dp_graphed_update()
+        out = engine.update_tensors(replay.sample(cfg.batch_size,
+                                                  graph_safe=True))
+        engine.update_iteration += 1
+        return out
 
     n_warm = (args.warmup + chunk - 1) // chunk if graphed else args.warmup
     for _ in range(n_warm):
@@ -202,15 +247,17 @@ def measure(engine, replay, cfg, args, device, ddp, rank,
         sync()
         t0 = time.perf_counter()
         for _ in range(args.steps // chunk if graphed else args.steps):
-            one_step()
+            last = one_step()
         sync()
         elapsed = time.perf_counter() - t0
+        if dump_dir is not None and not windows and rank == 0:
+            dump_outputs(dump_dir, engine, last)
         if ddp is not None:
             print(f"[bench {label} rank {rank}] window {len(windows)}: "
                   f"{elapsed * 1e3:.2f} ms local", file=sys.stderr)
             elapsed = ddp.max_scalar(elapsed)
         windows.append(elapsed)
-        if sum(windows) >= args.min_timed_seconds \
+        if not args.full or sum(windows) >= args.min_timed_seconds \
                 or len(windows) >= args.max_windows:
             break
     if ddp is not None:
@@ -319,18 +366,20 @@ def main():
                                              ddp=ddp)
 
     env_rate = None
-    if rank == 0 and not args.skip_rollout_probe:
+    if rank == 0 and args.full and not args.skip_rollout_probe:
         env_rate = rollout_probe(cfg, "cpu")
 
     med, n_windows, graph_mode = measure(engine, replay, cfg, args, device,
-                                         ddp, rank)
+                                         ddp, rank,
+                                         dump_dir=args.dump_outputs)
     steps_per_sec = args.steps / med
     value = n_gpus * steps_per_sec
 
     # auxiliary fp32 rate (the reference's own precision) — single-rank
     # only; reported as extra keys so the headline stays one dtype
     fp32_value = fp32_ms = None
-    if precision == "bf16" and world == 1 and not args.skip_fp32_probe:
+    if args.full and precision == "bf16" and world == 1 \
+            and not args.skip_fp32_probe:
         engine32, replay32 = build_engine_and_replay(cfg, device, "fp32",
                                                      rank, seed_off=1000)
         med32, _, _ = measure(engine32, replay32, cfg, args, device,

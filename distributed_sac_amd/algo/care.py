@@ -1015,7 +1015,7 @@ class CAREEngine(SACEngine):
                                       self._aloss_ws)
         daq, dlp = ext.actor_alpha_loss_bwd2(
             aq1, aq2, lp, states, la_det, al, self.alpha_group.flat_grad,
-            T, int(use_w), self.H_bar_f)
+            T, int(use_w), self.H_bar_f, self._dla_ws)
         if chain:
             empty_h = states.new_empty(0, dtype=torch.bfloat16)
             youts_f = [acts_f[i + 1] for i in range(nl_c - 1)] + [empty_h]

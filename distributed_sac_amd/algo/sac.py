@@ -219,6 +219,10 @@ class SACEngine:
         # reductions (per-block partial slots + self-resetting ticket)
         self._loss_ws = torch.zeros(256, device=dev)
         self._aloss_ws = torch.zeros(256, device=dev)
+        # same for the fixed-order alpha-gradient reduction of
+        # actor_alpha_loss_bwd2: ticket + (batch blocks x tasks) slots;
+        # a batch too large for it takes the kernel's one-block path
+        self._dla_ws = torch.zeros(2048, device=dev)
         # persistent counter for the in-kernel RNG, seeded from the torch
         # seed so runs stay reproducible end-to-end
         self._rng_ctr = torch.tensor(
@@ -796,7 +800,7 @@ class SACEngine:
                                       self._aloss_ws)
         daq, dlp = ext.actor_alpha_loss_bwd2(
             aq1, aq2, lp, states, la_det, al, self.alpha_group.flat_grad,
-            T, int(use_w), self.H_bar_f)
+            T, int(use_w), self.H_bar_f, self._dla_ws)
         if self._use_chain:
             empty_h = states.new_empty(0, dtype=torch.bfloat16)
             youts_f = [acts_f[i + 1] for i in range(nl_c - 1)] + [empty_h]

@@ -696,8 +696,9 @@ __global__ __launch_bounds__(256) void k_critic_loss_bwd(
 // single-workgroup fused variant (see k_critic_loss_fwd_1wg); writes
 // finalized out[0..3] + raw sums out[4..7] in one launch.  If dla is
 // non-null its first dla_n floats are zeroed here — the alpha gradient
-// buffer the subsequent k_actor_alpha_loss_bwd* atomics target — so the
-// engine needs no separate fill launch either.
+// buffer the subsequent k_actor_alpha_loss_bwd* kernels add their
+// fixed-order per-task sums to — so the engine needs no separate fill
+// launch either.
 // multi-block variant: each block reduces its stripe with wave shuffles
 // (one barrier), writes a private partial slot in ws, and the LAST block
 // (ticket in ws[0], self-resetting so graph replays stay correct) sums
@@ -870,9 +871,68 @@ __global__ __launch_bounds__(256) void k_actor_alpha_loss_fwd_1wg(
   }
 }
 
+// Per-task alpha gradient dla[t] += gal * -(1/B) sum_{i in t}(lp_i + H_bar),
+// reduced by ONE 256-thread block over all B rows in a fixed order, so the
+// result is bit-identical from run to run (float atomics are not: their
+// order varies, and the last-bit difference in log_alpha then feeds every
+// later update).  Each thread adds its rows (stride 256, ascending) into a
+// private LDS column; each task's 256 columns are then summed by one wave
+// in a fixed tree.  The k_actor_alpha_loss_bwd* kernels run it in one
+// extra block (the last of the grid), beside the elementwise blocks.
+// T <= 32 (checked on the host); the columns live in dynamic LDS, T*256
+// floats given at launch (none when the workspace path is taken).
+__device__ __forceinline__ void alpha_grad_block(
+    const float* __restrict__ lp, const float* __restrict__ onehot,
+    float* __restrict__ dla, float gal, int B, int T, int oh_stride,
+    float H_bar) {
+  extern __shared__ float s_acc[];
+  const int tid = threadIdx.x;
+  for (int t = 0; t < T; ++t) s_acc[t * 256 + tid] = 0.f;
+  // KR rows per thread at a time, the task argmax (same rule as
+  // task_of_row: first maximum wins) scanned t-outer / row-inner so the
+  // loads of one step are independent and overlap: the block takes a few
+  // memory round trips, not B/256 * T of them.  Rows past B are clamped
+  // for the loads and contribute +0.
+  constexpr int KR = 8;
+  for (int base = 0; base < B; base += 256 * KR) {
+    float best[KR], term[KR];
+    int ti[KR];
+    long row[KR];
+#pragma unroll
+    for (int k = 0; k < KR; ++k) {
+      const int i = base + k * 256 + tid;
+      row[k] = (long)(i < B ? i : B - 1);
+      term[k] = i < B ? gal * -(lp[row[k]] + H_bar) / (float)B : 0.f;
+      best[k] = -1e30f;
+      ti[k] = 0;
+    }
+    if (T > 1) {
+#pragma unroll 4
+      for (int t = 0; t < T; ++t) {
+#pragma unroll
+        for (int k = 0; k < KR; ++k) {
+          const float v = onehot[row[k] * oh_stride + t];
+          if (v > best[k]) { best[k] = v; ti[k] = t; }
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < KR; ++k) s_acc[ti[k] * 256 + tid] += term[k];
+  }
+  __syncthreads();
+  const int wid = tid >> 6, lane = tid & 63;
+  for (int t = wid; t < T; t += 4) {
+    const float* c = s_acc + t * 256;
+    float v = (c[lane] + c[lane + 64]) + (c[lane + 128] + c[lane + 192]);
+    v = wave_sum64(v);
+    if (lane == 0) dla[t] += v;
+  }
+}
+
 // daq1_i = gp*coeff_i*-(aq1<=aq2); daq2_i = gp*coeff_i*-(aq2<aq1)
 // dlp_i  = gp*coeff_i*alpha_i      (alpha detached in actor loss)
 // dla[t] = gal * -(1/B) sum_{i in t}(lp_i + H_bar)   (lp detached)
+// grid = ceil(B/256) elementwise blocks + 1 alpha-gradient block
 __global__ __launch_bounds__(256) void k_actor_alpha_loss_bwd(
     const float* __restrict__ aq1, const float* __restrict__ aq2,
     const float* __restrict__ lp, const float* __restrict__ onehot,
@@ -881,15 +941,16 @@ __global__ __launch_bounds__(256) void k_actor_alpha_loss_bwd(
     float* __restrict__ daq2, float* __restrict__ dlp,
     float* __restrict__ dla, int B, int T, int oh_stride, int use_w,
     float H_bar) {
+  if (blockIdx.x == gridDim.x - 1) {
+    alpha_grad_block(lp, onehot, dla, gscale[1], B, T, oh_stride, H_bar);
+    return;
+  }
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int tid = threadIdx.x;
-  __shared__ float s_dla[32];
   __shared__ float smw[32];
-  if (tid < T) s_dla[tid] = 0.f;
   if (use_w) fill_task_weights(smw, log_alpha, T);
   __syncthreads();
   if (i < B) {
-    const float gp = gscale[0], gal = gscale[1];
+    const float gp = gscale[0];
     const int t_i = task_of_row(onehot, i, oh_stride, T);
     const float alpha_i = __expf(log_alpha[t_i]);
     const float w_raw = use_w ? smw[t_i] : 1.f;
@@ -898,30 +959,48 @@ __global__ __launch_bounds__(256) void k_actor_alpha_loss_bwd(
     daq1[i] = first ? gp * coeff * -1.f : 0.f;
     daq2[i] = first ? 0.f : gp * coeff * -1.f;
     dlp[i] = gp * coeff * alpha_i;
-    atomicAdd(&s_dla[t_i], gal * -(lp[i] + H_bar) / (float)B);
   }
-  __syncthreads();
-  if (tid < T) atomicAdd(&dla[tid], s_dla[tid]);
 }
 
 // manual-backward actor/alpha variant: daq[2,B] bf16 stacked, dlp fp32,
-// dla accumulated into the caller buffer (zeroed by caller).
+// dla accumulated into the caller buffer (zeroed by caller).  Without a
+// workspace: same grid as above (extra alpha-gradient block).  With ws
+// (1 ticket + gridDim*T floats, ticket zero on entry and self-resetting
+// like k_*_loss_fwd_mb): grid = ceil(B/256); every block reduces its own
+// 256 rows per task in a fixed order into its ws slots — reusing the task
+// index it needs anyway — and the LAST block adds the slots to dla in
+// block order.  Also bit-identical from run to run, with no serial scan.
 __global__ __launch_bounds__(256) void k_actor_alpha_loss_bwd2(
     const float* __restrict__ aq1, const float* __restrict__ aq2,
     const float* __restrict__ lp, const float* __restrict__ onehot,
     const float* __restrict__ log_alpha, const float* __restrict__ saved,
     unsigned short* __restrict__ daq, float* __restrict__ dlp,
-    float* __restrict__ dla, int B, int T, int oh_stride, int use_w,
-    float H_bar) {
+    float* __restrict__ dla, float* __restrict__ ws, int B, int T,
+    int oh_stride, int use_w, float H_bar) {
+  if (ws == nullptr && blockIdx.x == gridDim.x - 1) {
+    alpha_grad_block(lp, onehot, dla, 1.f, B, T, oh_stride, H_bar);
+    return;
+  }
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const int tid = threadIdx.x;
-  __shared__ float s_dla[32];
   __shared__ float smw[32];
-  if (tid < T) s_dla[tid] = 0.f;
+  __shared__ float s_val[256];
+  __shared__ int s_t[256];
+  __shared__ int s_last;
   if (use_w) fill_task_weights(smw, log_alpha, T);
+  if (ws != nullptr) {
+    s_t[tid] = -1;
+    s_val[tid] = 0.f;
+    if (i < B) {
+      s_t[tid] = task_of_row(onehot, i, oh_stride, T);
+      s_val[tid] = -(lp[i] + H_bar) / (float)B;
+    }
+  }
   __syncthreads();
+  // elementwise part first: its loads overlap the reduction below
   if (i < B) {
-    const int t_i = task_of_row(onehot, i, oh_stride, T);
+    const int t_i = ws != nullptr ? s_t[tid]
+                                  : task_of_row(onehot, i, oh_stride, T);
     const float alpha_i = __expf(log_alpha[t_i]);
     const float w_raw = use_w ? smw[t_i] : 1.f;
     const float coeff = (use_w ? w_raw / saved[1] : 1.f) / (float)B;
@@ -935,10 +1014,33 @@ __global__ __launch_bounds__(256) void k_actor_alpha_loss_bwd2(
     daq[i] = cvt(first ? coeff * -1.f : 0.f);
     daq[B + i] = cvt(first ? 0.f : coeff * -1.f);
     dlp[i] = coeff * alpha_i;
-    atomicAdd(&s_dla[t_i], -(lp[i] + H_bar) / (float)B);
   }
-  __syncthreads();
-  if (tid < T) atomicAdd(&dla[tid], s_dla[tid]);
+  if (ws != nullptr) {
+    float* slots = ws + 1 + (long)blockIdx.x * T;
+    const int wid = tid >> 6, lane = tid & 63;
+    for (int t = wid; t < T; t += 4) {
+      float v = ((s_t[lane] == t ? s_val[lane] : 0.f) +
+                 (s_t[lane + 64] == t ? s_val[lane + 64] : 0.f)) +
+                ((s_t[lane + 128] == t ? s_val[lane + 128] : 0.f) +
+                 (s_t[lane + 192] == t ? s_val[lane + 192] : 0.f));
+      v = wave_sum64(v);
+      if (lane == 0) { slots[t] = v; __threadfence(); }
+    }
+    __syncthreads();
+    if (tid == 0) {
+      __threadfence();
+      const unsigned old = atomicAdd((unsigned*)ws, 1u);
+      s_last = (old == (unsigned)gridDim.x - 1u);
+      if (s_last) { *(unsigned*)ws = 0u; __threadfence(); }
+    }
+    __syncthreads();
+    if (s_last && tid < T) {
+      const volatile float* all = ws + 1;
+      float r = 0.f;
+      for (int b = 0; b < (int)gridDim.x; ++b) r += all[(long)b * T + tid];
+      dla[tid] += r;
+    }
+  }
 }
 
 // squash backward emitting the joined actor-head gradient [B, 2A] bf16
@@ -1467,8 +1569,10 @@ static std::vector<torch::Tensor> actor_alpha_loss_bwd(
   auto daq2 = torch::empty_like(aq2);
   auto dlp = torch::empty_like(lp);
   auto dla = torch::zeros_like(log_alpha);
-  hipLaunchKernelGGL(k_actor_alpha_loss_bwd, dim3((B + 255) / 256), dim3(256),
-                     0, cur_stream(), aq1.data_ptr<float>(),
+  TORCH_CHECK(T <= 32 && dla.numel() >= T, "alpha gradient: T <= 32");
+  hipLaunchKernelGGL(k_actor_alpha_loss_bwd, dim3((B + 255) / 256 + 1), dim3(256),
+                     (size_t)T * 256 * sizeof(float), cur_stream(),
+                     aq1.data_ptr<float>(),
                      aq2.data_ptr<float>(), lp.data_ptr<float>(), oh,
                      log_alpha.data_ptr<float>(), saved.data_ptr<float>(),
                      gscale.data_ptr<float>(), daq1.data_ptr<float>(),
@@ -1499,19 +1603,30 @@ static torch::Tensor critic_loss_bwd2(
 static std::vector<torch::Tensor> actor_alpha_loss_bwd2(
     torch::Tensor aq1, torch::Tensor aq2, torch::Tensor lp,
     torch::Tensor states, torch::Tensor log_alpha, torch::Tensor saved,
-    torch::Tensor dla_out, long T, long use_w, double H_bar) {
+    torch::Tensor dla_out, long T, long use_w, double H_bar,
+    c10::optional<torch::Tensor> ws = c10::nullopt) {
   CHECK_IN(aq1); CHECK_IN(dla_out);
   const long B = aq1.size(0);
   const long oh_stride = states.size(1);
   const float* oh = states.data_ptr<float>() + (oh_stride - T);
   auto daq = torch::empty({2, B, 1}, aq1.options().dtype(torch::kBFloat16));
   auto dlp = torch::empty_like(lp);
-  hipLaunchKernelGGL(k_actor_alpha_loss_bwd2, dim3((B + 255) / 256),
-                     dim3(256), 0, cur_stream(), aq1.data_ptr<float>(),
+  TORCH_CHECK(T <= 32 && dla_out.numel() >= T, "alpha gradient: T <= 32");
+  const long nblk = (B + 255) / 256;
+  float* ws_p = nullptr;   // ticket path only if the workspace is big enough
+  if (ws.has_value() && ws->numel() >= 1 + nblk * T) {
+    CHECK_IN(*ws);
+    ws_p = ws->data_ptr<float>();
+  }
+  hipLaunchKernelGGL(k_actor_alpha_loss_bwd2,
+                     dim3(ws_p ? nblk : nblk + 1),
+                     dim3(256),
+                     ws_p ? 0 : (size_t)T * 256 * sizeof(float),
+                     cur_stream(), aq1.data_ptr<float>(),
                      aq2.data_ptr<float>(), lp.data_ptr<float>(), oh,
                      log_alpha.data_ptr<float>(), saved.data_ptr<float>(),
                      (unsigned short*)daq.data_ptr(), dlp.data_ptr<float>(),
-                     dla_out.data_ptr<float>(), (int)B, (int)T,
+                     dla_out.data_ptr<float>(), ws_p, (int)B, (int)T,
                      (int)oh_stride, (int)use_w, (float)H_bar);
   return {daq, dlp};
 }
@@ -1712,7 +1827,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           pybind11::arg("ws") = pybind11::none());
   mod.def("actor_alpha_loss_bwd", &actor_alpha_loss_bwd);
   mod.def("critic_loss_bwd2", &critic_loss_bwd2);
-  mod.def("actor_alpha_loss_bwd2", &actor_alpha_loss_bwd2);
+  mod.def("actor_alpha_loss_bwd2", &actor_alpha_loss_bwd2,
+          pybind11::arg("aq1"), pybind11::arg("aq2"), pybind11::arg("lp"),
+          pybind11::arg("states"), pybind11::arg("log_alpha"),
+          pybind11::arg("saved"), pybind11::arg("dla_out"),
+          pybind11::arg("T"), pybind11::arg("use_w"), pybind11::arg("H_bar"),
+          pybind11::arg("ws") = pybind11::none());
   mod.def("squashed_gaussian_bwd2", &squashed_gaussian_bwd2);
   mod.def("adam_step_", &adam_step_);
   mod.def("adam_step_dev_", &adam_step_dev_,

@@ -31,6 +31,7 @@ are stubbed — none of their functionality is touched by update_SAC.
 
 import contextlib
 import importlib
+import os
 import sys
 import types
 
@@ -63,6 +64,9 @@ def ref_src(variant: str):
     """Import context for one reference variant's src/ directory."""
     _stub_external_deps()
     src = f"{REF}/{variant}/src"
+    assert os.path.isdir(src), (
+        f"these tests run the reference implementation's own sources and "
+        f"need its tree at {REF} (see README, 'Tests'); {src} is missing")
     saved = {n: sys.modules.pop(n) for n in list(_REF_MODULE_NAMES)
              if n in sys.modules}
     sys.path.insert(0, src)
