@@ -223,6 +223,9 @@ class SACEngine:
         # actor_alpha_loss_bwd2: ticket + (batch blocks x tasks) slots;
         # a batch too large for it takes the kernel's one-block path
         self._dla_ws = torch.zeros(2048, device=dev)
+        # the fused actor/alpha fwd+bwd kernel: one ticket, 32x4 metric
+        # slots, then up to 32 blocks x 32 tasks of alpha-gradient slots
+        self._aafb_ws = torch.zeros(1 + 32 * 4 + 32 * 32, device=dev)
         # persistent counter for the in-kernel RNG, seeded from the torch
         # seed so runs stay reproducible end-to-end
         self._rng_ctr = torch.tensor(
@@ -601,6 +604,17 @@ class SACEngine:
                 and getattr(self, "_rng_ctr", None) is not None
                 and _os.environ.get("DSAC_KRNG", "1") == "1")
 
+    @property
+    def _fuse_tail(self) -> bool:
+        """Fused small-kernel tail of the manual update: TD target + critic
+        loss fwd + bwd in one launch, actor/alpha loss fwd + bwd in one,
+        the split-K arena fold inside the Adam kernels (single-GPU only:
+        with DP the all-reduce sits between fold and Adam), and Polyak
+        inside the actor+alpha Adam launch.  Bit-identical results;
+        DSAC_FUSE_TAIL=0 restores the separate launches."""
+        import os as _os
+        return _os.environ.get("DSAC_FUSE_TAIL", "1") == "1"
+
     def _adam_prolog_all(self) -> bool:
         """ONE launch advances every optimizer's Adam state (+ RNG bump)
         at the top of seg2; the individual steppers then skip their own
@@ -706,8 +720,13 @@ class SACEngine:
             xt = torch.cat([next_states, na], dim=-1)
             q1_t, q2_t, _ = self._twin_fwd_manual(
                 xt, self._twin_target_bf16, self._twin_target[1])
-        y = ext.td_target_mt(rewards, dones, q1_t, q2_t, nlp, states,
-                             la_det, T, self.gamma, self.reward_scale)
+        fuse = self._fuse_tail
+        # one launch for TD target + loss fwd + dq (its grid covers the
+        # batch in <= 32 blocks); a larger batch keeps the three launches
+        fuse_loss = fuse and B <= 8192
+        if not fuse_loss:
+            y = ext.td_target_mt(rewards, dones, q1_t, q2_t, nlp, states,
+                                 la_det, T, self.gamma, self.reward_scale)
 
         # ---- critic loss + manual backward ---------------------------
         if chain:
@@ -720,10 +739,15 @@ class SACEngine:
             x = torch.cat([states, actions], dim=-1)
             q1, q2, acts_c = self._twin_fwd_manual(
                 x, self._twin_local_bf16, self._twin_local[1])
-        closs = ext.critic_loss_fwd(q1, q2, y, states, la_det, T,
-                                    int(use_w), self._loss_ws)[0]
-        dy = ext.critic_loss_bwd2(q1, q2, y, states, la_det, closs, T,
-                                  int(use_w))
+        if fuse_loss:
+            closs, dy = ext.critic_td_loss(
+                rewards, dones, q1_t, q2_t, nlp, q1, q2, states, la_det, T,
+                int(use_w), self.gamma, self.reward_scale, self._loss_ws)
+        else:
+            closs = ext.critic_loss_fwd(q1, q2, y, states, la_det, T,
+                                        int(use_w), self._loss_ws)[0]
+            dy = ext.critic_loss_bwd2(q1, q2, y, states, la_det, closs, T,
+                                      int(use_w))
         wsg = [w.grad for w in self._twin_local[0]]
         bsg = [b.grad for b in self._twin_local[1]]
         fg_c = self.critic_group.flat_grad
@@ -747,8 +771,13 @@ class SACEngine:
         else:
             self._mlp_bwd_arena(ext, dy, acts_c, self._twin_local_bf16,
                                 wsg, bsg, fg_c, arena_c, S_c, ch_c, G=2)
-        ext.reduce_arena(arena_c, fg_c, S_c)
+        # single-GPU: the critic Adam kernel folds the arena itself; with
+        # DP the all-reduce needs the folded gradient first
+        fold_c = fuse and self.ddp is None
+        if not fold_c:
+            ext.reduce_arena(arena_c, fg_c, S_c)
         self._dp_st = {
+            "fuse": fuse, "arena_c": (arena_c, S_c) if fold_c else None,
             "states": states, "sa": a_cat[B:], "lp": lp_cat[B:],
             "lsr": lsr, "ls_cat": ls_cat, "eps": eps, "tanh_u": tanh_u,
             "acts_a": acts_a, "ws_f32": ws_f32, "bs_f32": bs_f32,
@@ -766,7 +795,8 @@ class SACEngine:
         st = self._dp_st
         st["prolog"] = self._adam_prolog_all()
         # adam kernel also refreshes the bf16 mirror
-        self.critic_optimizer.step(pre_prologed=st["prolog"])
+        self.critic_optimizer.step(pre_prologed=st["prolog"],
+                                   arena=st["arena_c"])
 
         states, sa, lp = st["states"], st["sa"], st["lp"]
         B = st["B"]
@@ -794,13 +824,26 @@ class SACEngine:
                 xa, self._twin_local_bf16, self._twin_local[1])
         # the fwd kernel zeroes the alpha flat grad in passing (the bwd's
         # atomics target) — no separate fill launch
-        al = ext.actor_alpha_loss_fwd(aq1, aq2, lp, ls, states,
-                                      la_det, T, int(use_w), self.H_bar_f,
-                                      self.alpha_group.flat_grad,
-                                      self._aloss_ws)
-        daq, dlp = ext.actor_alpha_loss_bwd2(
-            aq1, aq2, lp, states, la_det, al, self.alpha_group.flat_grad,
-            T, int(use_w), self.H_bar_f, self._dla_ws)
+        fuse = st["fuse"]
+        if fuse and B <= 8192:
+            # forward metrics, dq/dlp and the alpha flat grad in one launch.
+            # The weighted-loss normalizer is the one the critic loss of
+            # this update finalized (closs[2]: same states, same log_alpha
+            # — alpha steps in seg3), so the blocks need not recompute it.
+            al, daq, dlp = ext.actor_alpha_loss_fwd_bwd(
+                aq1, aq2, lp, ls, states, la_det,
+                self.alpha_group.flat_grad, T, int(use_w), self.H_bar_f,
+                self._aafb_ws, st["closs"][2:3] if use_w else None)
+        else:
+            al = ext.actor_alpha_loss_fwd(aq1, aq2, lp, ls, states,
+                                          la_det, T, int(use_w),
+                                          self.H_bar_f,
+                                          self.alpha_group.flat_grad,
+                                          self._aloss_ws)
+            daq, dlp = ext.actor_alpha_loss_bwd2(
+                aq1, aq2, lp, states, la_det, al,
+                self.alpha_group.flat_grad, T, int(use_w), self.H_bar_f,
+                self._dla_ws)
         if self._use_chain:
             empty_h = states.new_empty(0, dtype=torch.bfloat16)
             youts_f = [acts_f[i + 1] for i in range(nl_c - 1)] + [empty_h]
@@ -858,24 +901,34 @@ class SACEngine:
                 if i > 0:
                     dy = ext.linear_bwd_dx_bf16(dy, self._actor_ws_bf16[i],
                                                 yout, act, 1, 1)
-        ext.reduce_arena(arena_a, fg_a, S_a)
+        fold_a = fuse and self.ddp is None
+        if not fold_a:
+            ext.reduce_arena(arena_a, fg_a, S_a)
+        st["arena_a"] = (arena_a, S_a) if fold_a else None
         st["al"] = al
 
     @torch.no_grad()
     def _manual_seg3(self):
         """Segment 3: fused actor+alpha Adam, Polyak target update."""
         st = self._dp_st
+        polyak = (self.target_group, self.critic_group, self.tau,
+                  getattr(self, "_target_bf16", None))
+        fuse = bool(st.get("fuse"))
+        # fused tail: the same launch folds the actor split-K arena and
+        # does the Polyak update (it reads the critic stepped in seg2)
         FusedAdam.step_many([self.actor_optimizer,
                              self.log_alpha_optimizer],
                             rng_bump=(None if st.get("prolog")
                                       else (self._rng_ctr if self._use_krng
                                             else None)),
-                            pre_prologed=bool(st.get("prolog")))
+                            pre_prologed=bool(st.get("prolog")),
+                            arena0=st.get("arena_a"),
+                            polyak=polyak if fuse else None)
         # NOTE: self.alpha is refreshed lazily (checkpoint/_per_sample_alpha
         # recompute from log_alpha) — an exp() here would replay as a
         # ~5 µs kernel every captured step just for bookkeeping
-        flat_polyak_(self.target_group, self.critic_group, self.tau,
-                     mirror=getattr(self, "_target_bf16", None))
+        if not fuse:
+            flat_polyak_(*polyak)
         closs, al = st["closs"], st["al"]
         return {
             "critic_loss": closs[6],  # summed in-kernel

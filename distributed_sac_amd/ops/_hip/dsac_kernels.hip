@@ -514,6 +514,19 @@ __global__ __launch_bounds__(256) void k_td_target(
   y[i] = rs * r[i] + gamma * (1.f - d[i]) * (fminf(q1[i], q2[i]) - alpha[i] * lp[i]);
 }
 
+// y for one row, with the operation sequence spelled out (one fused
+// multiply-add for min - alpha*lp, then two products and a sum) so that
+// every kernel that inlines it rounds alike whatever the contraction
+// heuristics make of the surrounding code.
+__device__ __forceinline__ float td_target_value(float rs, float r,
+                                                 float gamma, float d,
+                                                 float qmin, float alpha,
+                                                 float lp) {
+#pragma clang fp contract(off)
+  const float x = __builtin_fmaf(-alpha, lp, qmin);
+  return rs * r + gamma * (1.f - d) * x;
+}
+
 // K5b: MT variant — per-sample alpha computed in-kernel from
 // log_alpha[t_i] (one-hot suffix), removing the gather matmul
 // (reference learner.get_log_alpha, MT10…MTSAC/src/learner.py:213-233).
@@ -534,7 +547,8 @@ __global__ __launch_bounds__(256) void k_td_target_mt(
     }
   }
   const float alpha = __expf(log_alpha[t_i]);
-  y[i] = rs * r[i] + gamma * (1.f - d[i]) * (fminf(q1[i], q2[i]) - alpha * lp[i]);
+  y[i] = td_target_value(rs, r[i], gamma, d[i], fminf(q1[i], q2[i]), alpha,
+                         lp[i]);
 }
 
 // ---------------------------------------------------------------------------
@@ -1211,6 +1225,408 @@ __global__ __launch_bounds__(256) void k_polyak(
   if (mir != nullptr) mir[i] = f32_bf16_rne_d(tn);
 }
 
+// ---------------------------------------------------------------------------
+// Fused tail kernels: each folds a chain of strictly dependent neighbours
+// above into one launch.  The arithmetic and every reduction order are
+// those of the kernels they replace, so the results are bit-identical.
+// ---------------------------------------------------------------------------
+
+// Batch-wide sum of the per-row task weights — the wsum that the last block
+// of k_*_loss_fwd_mb finalizes — recomputed by EVERY block so the backward
+// coefficient needs no wait on other blocks.  Association order is the
+// multi-block forward's at grid = ceil(B/256) <= 32: one row per thread,
+// wave_sum64, the four wave partials left to right, blocks in index order.
+// The one-hot scan runs t-outer over KR blocks' rows so its loads overlap;
+// own_t receives the task of this thread's own row (blockIdx.x*256 + tid).
+// Ends with a barrier; wpart may be reused afterwards.
+struct __attribute__((packed, aligned(4))) OneHot4 { float v[4]; };
+struct __attribute__((packed, aligned(4))) OneHot2 { float v[2]; };
+
+__device__ __forceinline__ float batch_weight_sum(
+    const float* __restrict__ smw, const float* __restrict__ onehot,
+    float (*wpart)[4], int B, int T, int oh_stride, int nblk, int& own_t) {
+  const int tid = threadIdx.x, wid = tid >> 6, lane = tid & 63;
+  constexpr int KR = 8;
+  for (int b0 = 0; b0 < nblk; b0 += KR) {
+    float best[KR];
+    int ti[KR];
+    long row[KR];
+#pragma unroll
+    for (int k = 0; k < KR; ++k) {
+      const int i = (b0 + k) * 256 + tid;
+      row[k] = (long)(i < B ? i : B - 1);
+      best[k] = -1e30f;
+      ti[k] = 0;
+    }
+    if (T > 1) {
+      // a lane's row is its own cache line, so a load instruction costs the
+      // address path 64 lines whatever its width: read four (then two, then
+      // one) tasks per load.  The suffix is only 4-byte aligned.
+      int t = 0;
+#pragma unroll 2
+      for (; t + 4 <= T; t += 4) {
+#pragma unroll
+        for (int k = 0; k < KR; ++k) {
+          const OneHot4 q = *reinterpret_cast<const OneHot4*>(
+              onehot + row[k] * oh_stride + t);
+#pragma unroll
+          for (int c = 0; c < 4; ++c)
+            if (q.v[c] > best[k]) { best[k] = q.v[c]; ti[k] = t + c; }
+        }
+      }
+      if (t + 2 <= T) {
+#pragma unroll
+        for (int k = 0; k < KR; ++k) {
+          const OneHot2 q = *reinterpret_cast<const OneHot2*>(
+              onehot + row[k] * oh_stride + t);
+#pragma unroll
+          for (int c = 0; c < 2; ++c)
+            if (q.v[c] > best[k]) { best[k] = q.v[c]; ti[k] = t + c; }
+        }
+        t += 2;
+      }
+      if (t < T) {
+#pragma unroll
+        for (int k = 0; k < KR; ++k) {
+          const float v = onehot[row[k] * oh_stride + t];
+          if (v > best[k]) { best[k] = v; ti[k] = t; }
+        }
+      }
+    }
+    // the KR wave sums step together so their shuffles pipeline; each is
+    // the wave_sum64 sequence (rows past B and blocks past nblk add 0)
+    float w[KR];
+#pragma unroll
+    for (int k = 0; k < KR; ++k) {
+      const int i = (b0 + k) * 256 + tid;
+      w[k] = i < B ? smw[ti[k]] : 0.f;
+      if (b0 + k == (int)blockIdx.x) own_t = ti[k];
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+      for (int k = 0; k < KR; ++k) w[k] += __shfl_xor(w[k], off, 64);
+    }
+#pragma unroll
+    for (int k = 0; k < KR; ++k)
+      if (lane == 0 && b0 + k < nblk) wpart[b0 + k][wid] = w[k];
+  }
+  __syncthreads();
+  float r = 0.f;
+  for (int b = 0; b < nblk; ++b)
+    r += wpart[b][0] + wpart[b][1] + wpart[b][2] + wpart[b][3];
+  return r;
+}
+
+// K5b + K6 critic forward + backward in one launch: TD target, weighted MSE
+// sums (per-block slots, self-resetting ticket, last block finalizes in
+// block order — as k_critic_loss_fwd_mb) and dq[2,B] bf16 (as
+// k_critic_loss_bwd2).  grid = ceil(B/256) <= 32, i.e. B <= 8192.
+__global__ __launch_bounds__(256) void k_critic_td_loss(
+    const float* __restrict__ r, const float* __restrict__ d,
+    const float* __restrict__ q1t, const float* __restrict__ q2t,
+    const float* __restrict__ nlp, const float* __restrict__ q1,
+    const float* __restrict__ q2, const float* __restrict__ onehot,
+    const float* __restrict__ log_alpha, float* __restrict__ out,
+    float* __restrict__ ws, unsigned short* __restrict__ dq,
+    int B, int T, int oh_stride, int use_w, float gamma, float rs) {
+  __shared__ float part[3][4];
+  __shared__ float smw[32];
+  __shared__ float wpart[32][4];
+  __shared__ float s_fin[32 * 3];
+  __shared__ int s_last;
+  const int tid = threadIdx.x;
+  const int i = blockIdx.x * 256 + tid;
+  // the row's operands first (row clamped, so the loads are unconditional
+  // and in flight during the weight-sum recompute)
+  const long ic = i < B ? i : B - 1;
+  const float rv = r[ic], dv = d[ic], q1tv = q1t[ic], q2tv = q2t[ic];
+  const float lpv = nlp[ic], q1v = q1[ic], q2v = q2[ic];
+  int t_i = 0;
+  float wsum = 1.f;
+  if (use_w) {
+    fill_task_weights(smw, log_alpha, T);
+    __syncthreads();
+    wsum = batch_weight_sum(smw, onehot, wpart, B, T, oh_stride,
+                            (int)gridDim.x, t_i);
+  } else {
+    t_i = task_of_row(onehot, ic, oh_stride, T);
+  }
+  float s_l1 = 0.f, s_l2 = 0.f, s_w = 0.f;
+  if (i < B) {
+    const float alpha = __expf(log_alpha[t_i]);
+    const float y = td_target_value(rs, rv, gamma, dv, fminf(q1tv, q2tv),
+                                    alpha, lpv);
+    const float w_raw = use_w ? smw[t_i] : 1.f;
+    s_w += w_raw;
+    const float d1 = y - q1v, d2 = y - q2v;
+    s_l1 += w_raw * d1 * d1;
+    s_l2 += w_raw * d2 * d2;
+    const float coeff = (use_w ? w_raw / wsum : 1.f) / (float)B;
+    dq[i] = f32_bf16_rne_d(coeff * -2.f * (y - q1v));
+    dq[B + i] = f32_bf16_rne_d(coeff * -2.f * (y - q2v));
+  }
+  s_l1 = wave_sum64(s_l1); s_l2 = wave_sum64(s_l2); s_w = wave_sum64(s_w);
+  const int wid = tid >> 6;
+  if ((tid & 63) == 0) {
+    part[0][wid] = s_l1; part[1][wid] = s_l2; part[2][wid] = s_w;
+  }
+  __syncthreads();
+  float* slots = ws + 1;
+  if (tid == 0) {
+    slots[blockIdx.x * 3 + 0] =
+        part[0][0] + part[0][1] + part[0][2] + part[0][3];
+    slots[blockIdx.x * 3 + 1] =
+        part[1][0] + part[1][1] + part[1][2] + part[1][3];
+    slots[blockIdx.x * 3 + 2] =
+        part[2][0] + part[2][1] + part[2][2] + part[2][3];
+    __threadfence();
+    const unsigned old = atomicAdd((unsigned*)ws, 1u);
+    s_last = (old == (unsigned)gridDim.x - 1u);
+    if (s_last) {
+      *(unsigned*)ws = 0u;  // reset the ticket for the next replay
+      __threadfence();
+    }
+  }
+  __syncthreads();
+  if (!s_last) return;
+  // last block: one parallel read of every slot (a serial scan costs a
+  // memory round trip per slot), then the sums in block order
+  const int nb = (int)gridDim.x;
+  if (tid < nb * 3) s_fin[tid] = ((const volatile float*)slots)[tid];
+  __syncthreads();
+  if (tid == 0) {
+    float r0 = 0.f, r1 = 0.f, r2 = 0.f;
+    for (int b = 0; b < nb; ++b) {
+      r0 += s_fin[b * 3 + 0];
+      r1 += s_fin[b * 3 + 1];
+      r2 += s_fin[b * 3 + 2];
+    }
+    const float wfin = use_w ? r2 : 1.f;
+    const float denom = wfin * (float)B;
+    out[3] = r0; out[4] = r1; out[5] = r2;
+    out[0] = r0 / denom;
+    out[1] = r1 / denom;
+    out[2] = wfin;
+    out[6] = (r0 + r1) / denom;
+  }
+}
+
+// K6 actor/alpha forward + backward in one launch (k_actor_alpha_loss_fwd_mb
+// + the workspace path of k_actor_alpha_loss_bwd2).  ws = ticket, 32*4
+// metric slots, then gridDim*T alpha-gradient slots; ONE ticket serves both
+// finalizations.  dla[0..T) is stored as 0.f + r (the replaced pair zeroes
+// it and then adds r), dla[T..dla_n) as 0.f.  grid = ceil(B/256) <= 32.
+__global__ __launch_bounds__(256) void k_actor_alpha_loss_fwd_bwd(
+    const float* __restrict__ aq1, const float* __restrict__ aq2,
+    const float* __restrict__ lp, const float* __restrict__ ls,
+    const float* __restrict__ onehot, const float* __restrict__ log_alpha,
+    float* __restrict__ out, float* __restrict__ ws,
+    unsigned short* __restrict__ daq, float* __restrict__ dlp,
+    float* __restrict__ dla, int dla_n, const float* __restrict__ wsum_in,
+    int B, int T, int A, int oh_stride, int use_w, float H_bar) {
+  __shared__ float part[4][4];
+  __shared__ float smw[32];
+  __shared__ float wpart[32][4];
+  __shared__ float s_val[256];
+  __shared__ int s_t[256];
+  __shared__ int s_last;
+  __shared__ float s_fin[32 * 4];
+  __shared__ float s_g[32 * 32];
+  const int tid = threadIdx.x;
+  constexpr float CE = 1.4189385332046727f;  // 0.5*(1+log(2*pi))
+  const int i = blockIdx.x * 256 + tid;
+  // the row's operands first (row clamped, so the loads are unconditional
+  // and in flight during the weight-sum recompute)
+  const long ic = i < B ? i : B - 1;
+  const float aq1v = aq1[ic], aq2v = aq2[ic], lpv = lp[ic];
+  float ent = CE * A;
+  for (int a = 0; a < A; ++a) ent += ls[ic * A + a];
+  int t_i = 0;
+  float wsum = 1.f;
+  if (use_w) {
+    fill_task_weights(smw, log_alpha, T);
+    __syncthreads();
+  }
+  if (use_w && wsum_in == nullptr) {
+    wsum = batch_weight_sum(smw, onehot, wpart, B, T, oh_stride,
+                            (int)gridDim.x, t_i);
+  } else {
+    // wsum_in: the same sum, already finalized by a critic-loss kernel of
+    // this update over the same one-hots and log_alpha
+    if (use_w) wsum = wsum_in[0];
+    t_i = task_of_row(onehot, ic, oh_stride, T);
+  }
+  float s_pl = 0.f, s_w = 0.f, s_al = 0.f, s_en = 0.f;
+  s_t[tid] = -1;
+  s_val[tid] = 0.f;
+  if (i < B) {
+    s_t[tid] = t_i;
+    s_val[tid] = -(lpv + H_bar) / (float)B;
+    const float la = log_alpha[t_i];
+    const float alpha_i = __expf(la);
+    const float w_raw = use_w ? smw[t_i] : 1.f;
+    s_w += w_raw;
+    const float qmin = fminf(aq1v, aq2v);
+    s_pl += w_raw * -(qmin - alpha_i * lpv);
+    s_al += la * (lpv + H_bar);
+    s_en += ent;
+    const float coeff = (use_w ? w_raw / wsum : 1.f) / (float)B;
+    const bool first = aq1v <= aq2v;
+    daq[i] = f32_bf16_rne_d(first ? coeff * -1.f : 0.f);
+    daq[B + i] = f32_bf16_rne_d(first ? 0.f : coeff * -1.f);
+    dlp[i] = coeff * alpha_i;
+  }
+  s_pl = wave_sum64(s_pl); s_w = wave_sum64(s_w);
+  s_al = wave_sum64(s_al); s_en = wave_sum64(s_en);
+  const int wid = tid >> 6, lane = tid & 63;
+  if (lane == 0) {
+    part[0][wid] = s_pl; part[1][wid] = s_w;
+    part[2][wid] = s_al; part[3][wid] = s_en;
+  }
+  __syncthreads();
+  float* mslots = ws + 1;
+  float* gslots = ws + 1 + 32 * 4;
+  // per-task sums of this block's 256 rows, as k_actor_alpha_loss_bwd2:
+  // wave w takes tasks w, w+4, ...; four at a time so the shuffles pipeline
+  for (int t0 = wid; t0 < T; t0 += 16) {
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int t = t0 + 4 * j;   // t >= T matches no row: v = 0, not stored
+      v[j] = ((s_t[lane] == t ? s_val[lane] : 0.f) +
+              (s_t[lane + 64] == t ? s_val[lane + 64] : 0.f)) +
+             ((s_t[lane + 128] == t ? s_val[lane + 128] : 0.f) +
+              (s_t[lane + 192] == t ? s_val[lane + 192] : 0.f));
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] += __shfl_xor(v[j], off, 64);
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (t0 + 4 * j < T) gslots[(long)blockIdx.x * T + t0 + 4 * j] = v[j];
+      __threadfence();
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      mslots[blockIdx.x * 4 + k] =
+          part[k][0] + part[k][1] + part[k][2] + part[k][3];
+    __threadfence();
+    const unsigned old = atomicAdd((unsigned*)ws, 1u);
+    s_last = (old == (unsigned)gridDim.x - 1u);
+    if (s_last) { *(unsigned*)ws = 0u; __threadfence(); }
+  }
+  __syncthreads();
+  if (!s_last) return;
+  // last block: parallel reads of every slot into LDS (a serial scan costs
+  // a memory round trip per slot), then the sums in block order
+  const int nb = (int)gridDim.x;
+  if (tid < nb * 4) s_fin[tid] = ((const volatile float*)mslots)[tid];
+  for (int k = tid; k < nb * T; k += 256)
+    s_g[k] = ((const volatile float*)gslots)[k];
+  __syncthreads();
+  if (tid < dla_n) {
+    float g = 0.f;
+    if (tid < T) {
+      float rsum = 0.f;
+      for (int b = 0; b < nb; ++b) rsum += s_g[b * T + tid];
+      g = 0.f + rsum;
+    }
+    dla[tid] = g;
+  }
+  if (tid == 0) {
+    float r0 = 0.f, r1 = 0.f, r2 = 0.f, r3 = 0.f;
+    for (int b = 0; b < nb; ++b) {
+      r0 += s_fin[b * 4 + 0]; r1 += s_fin[b * 4 + 1];
+      r2 += s_fin[b * 4 + 2]; r3 += s_fin[b * 4 + 3];
+    }
+    const float wfin = use_w ? r1 : 1.f;
+    out[4] = r0; out[5] = r1; out[6] = r2; out[7] = r3;
+    out[0] = r0 / (wfin * (float)B);
+    out[1] = wfin;
+    out[2] = -r2 / (float)B;
+    out[3] = r3 / (float)B;
+  }
+}
+
+// K9b that folds the split-K arena itself: g = sum_s arena[s*stride+i] from
+// 0.f in s order (k_reduce_arena), written back to the flat gradient for
+// callers that read .grad, then the unchanged Adam math + mirror store.
+__global__ __launch_bounds__(256) void k_adam_dev_arena(
+    float* __restrict__ p, float* __restrict__ g,
+    float* __restrict__ m, float* __restrict__ v,
+    const float* __restrict__ state, long n, float b1, float b2, float eps,
+    unsigned short* __restrict__ mir, const float* __restrict__ arena,
+    long stride, int S) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float step_size = state[1], inv_sqrt_bc2 = state[2];
+  float acc = 0.f;
+  for (int s = 0; s < S; ++s) acc += arena[(long)s * stride + i];
+  g[i] = acc;
+  const float gi = acc;
+  const float mi = b1 * m[i] + (1.f - b1) * gi;
+  const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+  m[i] = mi;
+  v[i] = vi;
+  const float pn = p[i] - step_size * mi / (sqrtf(vi) * inv_sqrt_bc2 + eps);
+  p[i] = pn;
+  if (mir != nullptr) mir[i] = f32_bf16_rne_d(pn);
+}
+
+// K9c + K10 in one launch: the index-range dispatch of k_adam_multi with
+// (a) an optional split-K arena folded into group 0's gradient as above and
+// (b) a trailing Polyak range (pt <- (1-tau)*pt + tau*psrc, + bf16 mirror).
+// The Polyak source must not be one of the Adam groups of this launch.
+__global__ __launch_bounds__(256) void k_adam_multi_tail(
+    float* p0, float* g0, float* m0, float* v0, const float* st0, long n0,
+    float* p1, const float* g1, float* m1, float* v1, const float* st1, long n1,
+    float* p2, const float* g2, float* m2, float* v2, const float* st2, long n2,
+    float b1, float b2, float eps, unsigned short* mr0, unsigned short* mr1,
+    unsigned short* mr2, const float* __restrict__ arena0, long stride0,
+    int S0, float* __restrict__ pt, const float* __restrict__ psrc, long np,
+    float tau, unsigned short* __restrict__ pmir) {
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  float* p; const float* g; float* m; float* v; const float* st;
+  unsigned short* mr;
+  bool fold = false;
+  if (i < n0) {
+    p = p0; g = g0; m = m0; v = v0; st = st0; mr = mr0;
+    fold = arena0 != nullptr;
+  }
+  else if ((i -= n0) < n1) { p = p1; g = g1; m = m1; v = v1; st = st1; mr = mr1; }
+  else if ((i -= n1) < n2) { p = p2; g = g2; m = m2; v = v2; st = st2; mr = mr2; }
+  else if ((i -= n2) < np) {
+    const float tn = (1.f - tau) * pt[i] + tau * psrc[i];
+    pt[i] = tn;
+    if (pmir != nullptr) pmir[i] = f32_bf16_rne_d(tn);
+    return;
+  }
+  else return;
+  float gi;
+  if (fold) {
+    float acc = 0.f;
+    for (int s = 0; s < S0; ++s) acc += arena0[(long)s * stride0 + i];
+    g0[i] = acc;
+    gi = acc;
+  } else {
+    gi = g[i];
+  }
+  const float mi = b1 * m[i] + (1.f - b1) * gi;
+  const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+  m[i] = mi;
+  v[i] = vi;
+  const float pn = p[i] - st[1] * mi / (sqrtf(vi) * st[2] + eps);
+  p[i] = pn;
+  if (mr != nullptr) mr[i] = f32_bf16_rne_d(pn);
+}
+
 // ===========================================================================
 // Host wrappers
 // ===========================================================================
@@ -1631,6 +2047,98 @@ static std::vector<torch::Tensor> actor_alpha_loss_bwd2(
   return {daq, dlp};
 }
 
+// td_target_mt + critic_loss_fwd(ws) + critic_loss_bwd2 in one launch.
+// Returns {closs[8], dq[2,B,1] bf16}; ws as for critic_loss_fwd.
+static std::vector<torch::Tensor> critic_td_loss(
+    torch::Tensor r, torch::Tensor d, torch::Tensor q1t, torch::Tensor q2t,
+    torch::Tensor nlp, torch::Tensor q1, torch::Tensor q2,
+    torch::Tensor states, torch::Tensor log_alpha, long T, long use_w,
+    double gamma, double rs, torch::Tensor ws) {
+  CHECK_IN(r); CHECK_IN(d); CHECK_IN(q1t); CHECK_IN(q2t); CHECK_IN(nlp);
+  CHECK_IN(q1); CHECK_IN(q2); CHECK_IN(states); CHECK_IN(log_alpha);
+  CHECK_IN(ws);
+  const long B = q1.size(0);
+  const long nblk = (B + 255) / 256;
+  TORCH_CHECK(B >= 1 && nblk <= 32, "critic_td_loss: 1 <= B <= 8192");
+  TORCH_CHECK(T >= 1 && T <= 32 && log_alpha.numel() >= T, "T <= 32");
+  TORCH_CHECK(ws.numel() >= 1 + 32 * 3, "workspace too small");
+  TORCH_CHECK(states.dim() == 2 && states.is_contiguous()
+              && states.size(0) == B && states.size(1) >= T);
+  auto rc = r.contiguous(); auto dc = d.contiguous();
+  auto q1tc = q1t.contiguous(); auto q2tc = q2t.contiguous();
+  auto lpc = nlp.contiguous();
+  auto q1c = q1.contiguous(); auto q2c = q2.contiguous();
+  TORCH_CHECK(rc.numel() == B && dc.numel() == B && q1tc.numel() == B
+              && q2tc.numel() == B && lpc.numel() == B && q1c.numel() == B
+              && q2c.numel() == B, "critic_td_loss: B elements per input");
+  const long oh_stride = states.size(1);
+  const float* oh = states.data_ptr<float>() + (oh_stride - T);
+  auto out = torch::empty({8}, q1.options());
+  auto dq = torch::empty({2, B, 1}, q1.options().dtype(torch::kBFloat16));
+  hipLaunchKernelGGL(k_critic_td_loss, dim3(nblk), dim3(256), 0,
+                     cur_stream(), rc.data_ptr<float>(),
+                     dc.data_ptr<float>(), q1tc.data_ptr<float>(),
+                     q2tc.data_ptr<float>(), lpc.data_ptr<float>(),
+                     q1c.data_ptr<float>(), q2c.data_ptr<float>(), oh,
+                     log_alpha.data_ptr<float>(), out.data_ptr<float>(),
+                     ws.data_ptr<float>(), (unsigned short*)dq.data_ptr(),
+                     (int)B, (int)T, (int)oh_stride, (int)use_w,
+                     (float)gamma, (float)rs);
+  return {out, dq};
+}
+
+// actor_alpha_loss_fwd(ws, dla) + actor_alpha_loss_bwd2(ws) in one launch.
+// Returns {al[8], daq[2,B,1] bf16, dlp}; dla (the alpha flat gradient) is
+// overwritten.  ws: 1 + 32*4 + ceil(B/256)*T floats, ticket zero on entry.
+// wsum (optional, 1 float): the weighted-loss normalizer a critic-loss
+// kernel finalized (closs[2]) over the SAME states and log_alpha with the
+// same B — the value this kernel's forward would compute; given it, the
+// blocks skip recomputing it for the backward coefficient.
+static std::vector<torch::Tensor> actor_alpha_loss_fwd_bwd(
+    torch::Tensor aq1, torch::Tensor aq2, torch::Tensor lp, torch::Tensor ls,
+    torch::Tensor states, torch::Tensor log_alpha, torch::Tensor dla,
+    long T, long use_w, double H_bar, torch::Tensor ws,
+    c10::optional<torch::Tensor> wsum = c10::nullopt) {
+  CHECK_IN(aq1); CHECK_IN(aq2); CHECK_IN(lp); CHECK_IN(ls);
+  CHECK_IN(states); CHECK_IN(log_alpha); CHECK_IN(dla); CHECK_IN(ws);
+  const float* wsum_p = nullptr;
+  if (wsum.has_value() && wsum->defined() && wsum->numel() > 0) {
+    CHECK_IN(*wsum);
+    wsum_p = wsum->data_ptr<float>();
+  }
+  const long B = aq1.size(0);
+  const long nblk = (B + 255) / 256;
+  TORCH_CHECK(B >= 1 && nblk <= 32,
+              "actor_alpha_loss_fwd_bwd: 1 <= B <= 8192");
+  TORCH_CHECK(T >= 1 && T <= 32 && log_alpha.numel() >= T
+              && dla.numel() >= T && dla.numel() <= 256
+              && dla.is_contiguous(), "alpha gradient: T <= 32");
+  TORCH_CHECK(ws.numel() >= 1 + 32 * 4 + nblk * T, "workspace too small");
+  TORCH_CHECK(states.dim() == 2 && states.is_contiguous()
+              && states.size(0) == B && states.size(1) >= T);
+  auto aq1c = aq1.contiguous(); auto aq2c = aq2.contiguous();
+  auto lpc = lp.contiguous(); auto lsc = ls.contiguous();
+  TORCH_CHECK(aq1c.numel() == B && aq2c.numel() == B && lpc.numel() == B
+              && lsc.dim() == 2 && lsc.size(0) == B,
+              "actor_alpha_loss_fwd_bwd: B rows per input");
+  const long A = lsc.size(1);
+  const long oh_stride = states.size(1);
+  const float* oh = states.data_ptr<float>() + (oh_stride - T);
+  auto out = torch::empty({8}, aq1.options());
+  auto daq = torch::empty({2, B, 1}, aq1.options().dtype(torch::kBFloat16));
+  auto dlp = torch::empty_like(lpc);
+  hipLaunchKernelGGL(k_actor_alpha_loss_fwd_bwd, dim3(nblk), dim3(256), 0,
+                     cur_stream(), aq1c.data_ptr<float>(),
+                     aq2c.data_ptr<float>(), lpc.data_ptr<float>(),
+                     lsc.data_ptr<float>(), oh, log_alpha.data_ptr<float>(),
+                     out.data_ptr<float>(), ws.data_ptr<float>(),
+                     (unsigned short*)daq.data_ptr(), dlp.data_ptr<float>(),
+                     dla.data_ptr<float>(), (int)dla.numel(), wsum_p, (int)B,
+                     (int)T, (int)A, (int)oh_stride, (int)use_w,
+                     (float)H_bar);
+  return {out, daq, dlp};
+}
+
 static torch::Tensor squashed_gaussian_bwd2(
     torch::Tensor ga, torch::Tensor gl, torch::Tensor lsr, torch::Tensor ls,
     torch::Tensor eps, torch::Tensor tanh_u, double k) {
@@ -1676,10 +2184,22 @@ static void adam_step_dev_(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                            torch::Tensor v, torch::Tensor state, double lr,
                            double b1, double b2, double eps,
                            c10::optional<torch::Tensor> mir_opt,
-                           long skip_prolog = 0) {
+                           long skip_prolog = 0,
+                           c10::optional<torch::Tensor> arena = c10::nullopt,
+                           long S = 0) {
   CHECK_IN(p); CHECK_IN(state);
   TORCH_CHECK(state.numel() >= 3, "state = {step, step_size, inv_sqrt_bc2}");
   const long n = p.numel();
+  // optional [>=S, n] split-K arena: the kernel folds it into g itself
+  const float* ap = nullptr;
+  if (arena.has_value() && arena->defined() && arena->numel() > 0) {
+    CHECK_IN(*arena); CHECK_IN(g);
+    TORCH_CHECK(arena->dim() == 2 && arena->is_contiguous()
+                && g.is_contiguous() && arena->size(1) == n
+                && g.numel() == n && S >= 1 && S <= arena->size(0),
+                "arena must be [>=S, numel]");
+    ap = arena->data_ptr<float>();
+  }
   unsigned short* mp = nullptr;
   if (mir_opt.has_value() && mir_opt->defined() && mir_opt->numel() > 0) {
     TORCH_CHECK(mir_opt->numel() == n
@@ -1690,6 +2210,14 @@ static void adam_step_dev_(torch::Tensor p, torch::Tensor g, torch::Tensor m,
     hipLaunchKernelGGL(k_adam_prolog, dim3(1), dim3(1), 0, cur_stream(),
                        state.data_ptr<float>(), (float)lr, (float)b1,
                        (float)b2);
+  if (ap != nullptr) {
+    hipLaunchKernelGGL(k_adam_dev_arena, dim3((n + 255) / 256), dim3(256), 0,
+                       cur_stream(), p.data_ptr<float>(),
+                       g.data_ptr<float>(), m.data_ptr<float>(),
+                       v.data_ptr<float>(), state.data_ptr<float>(), n,
+                       (float)b1, (float)b2, (float)eps, mp, ap, n, (int)S);
+    return;
+  }
   hipLaunchKernelGGL(k_adam_dev, dim3((n + 255) / 256), dim3(256), 0,
                      cur_stream(), p.data_ptr<float>(), g.data_ptr<float>(),
                      m.data_ptr<float>(), v.data_ptr<float>(),
@@ -1725,7 +2253,13 @@ static void adam_step_multi_(std::vector<torch::Tensor> ps,
                              std::vector<double> lrs, double b1, double b2,
                              double eps, std::vector<torch::Tensor> mirs,
                              c10::optional<torch::Tensor> rng = c10::nullopt,
-                             long skip_prolog = 0) {
+                             long skip_prolog = 0,
+                             c10::optional<torch::Tensor> arena0 = c10::nullopt,
+                             long S0 = 0,
+                             c10::optional<torch::Tensor> polyak_t = c10::nullopt,
+                             c10::optional<torch::Tensor> polyak_s = c10::nullopt,
+                             double tau = 0.0,
+                             c10::optional<torch::Tensor> polyak_mir = c10::nullopt) {
   const size_t G = ps.size();
   TORCH_CHECK(G >= 1 && G <= 3, "1..3 groups");
   float* P[3] = {nullptr, nullptr, nullptr};
@@ -1759,6 +2293,48 @@ static void adam_step_multi_(std::vector<torch::Tensor> ps,
     hipLaunchKernelGGL(k_adam_prolog3, dim3(1), dim3(3), 0, cur_stream(),
                        rng_p, St[0], St[1], St[2], (float)LR[0],
                        (float)LR[1], (float)LR[2], (float)b1, (float)b2);
+  // optional extras: split-K arena folded into group 0's gradient, and a
+  // Polyak range appended behind the Adam groups (k_adam_multi_tail)
+  const float* ap = nullptr;
+  if (arena0.has_value() && arena0->defined() && arena0->numel() > 0) {
+    CHECK_IN(*arena0); CHECK_IN(gs[0]);
+    TORCH_CHECK(arena0->dim() == 2 && arena0->is_contiguous()
+                && gs[0].is_contiguous() && arena0->size(1) == N[0]
+                && gs[0].numel() == N[0] && S0 >= 1
+                && S0 <= arena0->size(0), "arena0 must be [>=S0, numel0]");
+    ap = arena0->data_ptr<float>();
+  }
+  float* pt = nullptr; const float* psrc = nullptr; long np = 0;
+  unsigned short* pmir = nullptr;
+  if (polyak_t.has_value() && polyak_t->defined() && polyak_t->numel() > 0) {
+    TORCH_CHECK(polyak_s.has_value(), "polyak source missing");
+    CHECK_IN(*polyak_t); CHECK_IN(*polyak_s);
+    np = polyak_t->numel();
+    TORCH_CHECK(polyak_s->numel() == np && polyak_t->is_contiguous()
+                && polyak_s->is_contiguous(), "polyak buffers must match");
+    for (size_t g = 0; g < G; ++g)
+      TORCH_CHECK(polyak_s->data_ptr() != ps[g].data_ptr()
+                  && polyak_t->data_ptr() != ps[g].data_ptr(),
+                  "polyak buffers must not be stepped in the same launch");
+    pt = polyak_t->data_ptr<float>();
+    psrc = polyak_s->data_ptr<float>();
+    if (polyak_mir.has_value() && polyak_mir->defined()
+        && polyak_mir->numel() > 0) {
+      TORCH_CHECK(polyak_mir->numel() == np
+                  && polyak_mir->scalar_type() == torch::kBFloat16);
+      pmir = (unsigned short*)polyak_mir->data_ptr();
+    }
+  }
+  if (ap != nullptr || pt != nullptr) {
+    hipLaunchKernelGGL(k_adam_multi_tail, dim3((total + np + 255) / 256),
+                       dim3(256), 0, cur_stream(),
+                       P[0], gs[0].data_ptr<float>(), M[0], V[0], St[0], N[0],
+                       P[1], Gr[1], M[1], V[1], St[1], N[1],
+                       P[2], Gr[2], M[2], V[2], St[2], N[2],
+                       (float)b1, (float)b2, (float)eps, MR[0], MR[1], MR[2],
+                       ap, N[0], (int)S0, pt, psrc, np, (float)tau, pmir);
+    return;
+  }
   hipLaunchKernelGGL(k_adam_multi, dim3((total + 255) / 256), dim3(256), 0,
                      cur_stream(),
                      P[0], Gr[0], M[0], V[0], St[0], N[0],
@@ -1833,6 +2409,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           pybind11::arg("saved"), pybind11::arg("dla_out"),
           pybind11::arg("T"), pybind11::arg("use_w"), pybind11::arg("H_bar"),
           pybind11::arg("ws") = pybind11::none());
+  mod.def("critic_td_loss", &critic_td_loss,
+          pybind11::arg("r"), pybind11::arg("d"), pybind11::arg("q1t"),
+          pybind11::arg("q2t"), pybind11::arg("nlp"), pybind11::arg("q1"),
+          pybind11::arg("q2"), pybind11::arg("states"),
+          pybind11::arg("log_alpha"), pybind11::arg("T"),
+          pybind11::arg("use_w"), pybind11::arg("gamma"),
+          pybind11::arg("rs"), pybind11::arg("ws"));
+  mod.def("actor_alpha_loss_fwd_bwd", &actor_alpha_loss_fwd_bwd,
+          pybind11::arg("aq1"), pybind11::arg("aq2"), pybind11::arg("lp"),
+          pybind11::arg("ls"), pybind11::arg("states"),
+          pybind11::arg("log_alpha"), pybind11::arg("dla"),
+          pybind11::arg("T"), pybind11::arg("use_w"), pybind11::arg("H_bar"),
+          pybind11::arg("ws"), pybind11::arg("wsum") = pybind11::none());
   mod.def("squashed_gaussian_bwd2", &squashed_gaussian_bwd2);
   mod.def("adam_step_", &adam_step_);
   mod.def("adam_step_dev_", &adam_step_dev_,
@@ -1840,14 +2429,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           pybind11::arg("v"), pybind11::arg("state"), pybind11::arg("lr"),
           pybind11::arg("b1"), pybind11::arg("b2"), pybind11::arg("eps"),
           pybind11::arg("mir") = pybind11::none(),
-          pybind11::arg("skip_prolog") = 0);
+          pybind11::arg("skip_prolog") = 0,
+          pybind11::arg("arena") = pybind11::none(),
+          pybind11::arg("S") = 0);
   mod.def("adam_step_multi_", &adam_step_multi_,
           pybind11::arg("ps"), pybind11::arg("gs"), pybind11::arg("ms"),
           pybind11::arg("vs"), pybind11::arg("states"), pybind11::arg("lrs"),
           pybind11::arg("b1"), pybind11::arg("b2"), pybind11::arg("eps"),
           pybind11::arg("mirs") = std::vector<torch::Tensor>(),
           pybind11::arg("rng") = pybind11::none(),
-          pybind11::arg("skip_prolog") = 0);
+          pybind11::arg("skip_prolog") = 0,
+          pybind11::arg("arena0") = pybind11::none(),
+          pybind11::arg("S0") = 0,
+          pybind11::arg("polyak_t") = pybind11::none(),
+          pybind11::arg("polyak_s") = pybind11::none(),
+          pybind11::arg("tau") = 0.0,
+          pybind11::arg("polyak_mir") = pybind11::none());
   mod.def("adam_prolog_many", &adam_prolog_many,
           pybind11::arg("states"), pybind11::arg("lrs"),
           pybind11::arg("b1"), pybind11::arg("b2"),

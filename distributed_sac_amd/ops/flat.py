@@ -172,16 +172,30 @@ class FusedAdam:
         self.group.zero_grad()
 
     @torch.no_grad()
-    def step(self, pre_prologed: bool = False) -> None:
+    def step(self, pre_prologed: bool = False, arena=None) -> None:
+        """arena: optional ``(tensor [>=S, numel], S)`` of split-K gradient
+        partials — the Adam kernel sums them (s order, as reduce_arena),
+        writes the sum to the flat gradient and steps, in one launch."""
         p, g = self.group.flat_data, self.group.flat_grad
         m, v = self.exp_avg, self.exp_avg_sq
         b1, b2 = self.betas
         if self._dev_state is not None:
+            if arena is not None:
+                native().adam_step_dev_(p, g, m, v, self._dev_state,
+                                        self.lr, b1, b2, self.eps,
+                                        self.bf16_mirror,
+                                        1 if pre_prologed else 0,
+                                        arena[0], int(arena[1]))
+                return
             native().adam_step_dev_(p, g, m, v, self._dev_state,
                                     self.lr, b1, b2, self.eps,
                                     self.bf16_mirror,
                                     1 if pre_prologed else 0)
             return
+        if arena is not None:
+            g.zero_()
+            for s in range(int(arena[1])):
+                g.add_(arena[0][s])
         self._step_count += 1
         bc1 = 1 - b1 ** self._step_count
         bc2 = 1 - b2 ** self._step_count
@@ -193,19 +207,29 @@ class FusedAdam:
     @staticmethod
     @torch.no_grad()
     def step_many(opts: List["FusedAdam"], rng_bump=None,
-                  pre_prologed: bool = False) -> None:
+                  pre_prologed: bool = False, arena0=None,
+                  polyak=None) -> None:
         """Step up to 3 optimizers in ONE fused kernel launch (same betas/
         eps; device-resident step state required).  rng_bump: optional
         int64 counter the prolog kernel increments once — the per-update
         bump for the counter-based device RNG (race-free: the prolog is a
         single-block kernel and every RNG consumer runs in other
-        launches)."""
+        launches); with ``pre_prologed`` the caller's prolog has bumped it
+        already.
+
+        arena0: optional ``(tensor [>=S, numel], S)`` split-K partials of
+        the FIRST optimizer's gradient, summed inside the same launch (see
+        :meth:`step`).  polyak: optional ``(target, source, tau, mirror)``
+        — ``flat_polyak_(target, source, tau, mirror)`` done by the same
+        launch; ``source`` must not be one of ``opts``' groups."""
         live = [o for o in opts if o is not None]
+        assert arena0 is None or (opts and opts[0] is not None), \
+            "arena0 belongs to the first optimizer"
         if (1 <= len(live) <= 3
                 and all(o._dev_state is not None for o in live)
                 and all(o.betas == live[0].betas and o.eps == live[0].eps
                         for o in live)):
-            native().adam_step_multi_(
+            args = [
                 [o.group.flat_data for o in live],
                 [o.group.flat_grad for o in live],
                 [o.exp_avg for o in live],
@@ -215,10 +239,25 @@ class FusedAdam:
                 live[0].betas[0], live[0].betas[1], live[0].eps,
                 [o.bf16_mirror if o.bf16_mirror is not None
                  else torch.Tensor() for o in live],
-                rng_bump, 1 if pre_prologed else 0)
+                rng_bump, 1 if pre_prologed else 0]
+            if arena0 is not None or polyak is not None:
+                args += [arena0[0] if arena0 is not None else None,
+                         int(arena0[1]) if arena0 is not None else 0]
+                if polyak is not None:
+                    target, source, tau, mirror = polyak
+                    assert target.numel == source.numel
+                    args += [target.flat_data, source.flat_data, float(tau),
+                             mirror]
+            native().adam_step_multi_(*args)
             return
-        for o in live:
-            o.step()
+        # unfused fallback: same effects, one launch each
+        if rng_bump is not None and not pre_prologed:
+            rng_bump.add_(1)
+        for j, o in enumerate(live):
+            o.step(pre_prologed=pre_prologed,
+                   arena=arena0 if (j == 0 and o is opts[0]) else None)
+        if polyak is not None:
+            flat_polyak_(*polyak)
 
     # -- torch.optim.Adam-compatible (de)serialization ---------------------
 
