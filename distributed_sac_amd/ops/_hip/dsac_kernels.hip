@@ -433,6 +433,61 @@ __global__ __launch_bounds__(256) void k_replay_sample(
 }
 
 // ---------------------------------------------------------------------------
+// K12b: packed replay ingest — the write path of the [T, cap, D] rings.
+// One launch scatters a whole packed batch (docs/KERNELS.md "packed replay
+// batch"): header words [n_desc, T, total_rows, used], T float sizes, then
+// 8-word descriptors {task, n, first, rows, offset, dst_row, row_base, 0}
+// and the block payloads in ring-slot layout.  The host validates every
+// descriptor and guarantees that no two rows of one batch share a
+// destination, so plain stores suffice.
+// ---------------------------------------------------------------------------
+constexpr int PK_HDR = 4;    // header words before the sizes
+constexpr int PK_DESC = 8;   // words per descriptor
+
+__global__ __launch_bounds__(256) void k_replay_ingest(
+    const float* __restrict__ pk, float* __restrict__ states,
+    float* __restrict__ actions, float* __restrict__ rewards,
+    float* __restrict__ next_states, float* __restrict__ dones,
+    float* __restrict__ sizes, int n_desc, int total_rows, int T, long cap,
+    int Ds, int Da) {
+  if (blockIdx.x == 0)
+    for (int t = threadIdx.x; t < T; t += blockDim.x)
+      sizes[t] = pk[PK_HDR + t];
+  // one wave per ingested row: lanes stride the row's columns
+  const int i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (i >= total_rows) return;
+  const int* desc = reinterpret_cast<const int*>(pk) + PK_HDR + T;
+  // last descriptor with row_base <= i (row_base is a running sum of rows)
+  int lo = 0, hi = n_desc - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (desc[mid * PK_DESC + 6] <= i) lo = mid; else hi = mid - 1;
+  }
+  const int* d = desc + lo * PK_DESC;
+  const long t = d[0], n = d[1];
+  const long r = i - d[6];
+  const long srow = d[2] + r;
+  const long drow = t * cap + (d[5] + r) % cap;
+  const float* p = pk + d[4];
+  const float* p_s = p + srow * Ds;
+  const float* p_a = p + n * Ds + srow * Da;
+  const float* p_r = p + n * (Ds + Da) + srow;
+  const float* p_ns = p + n * (Ds + Da + 1) + srow * Ds;
+  const float* p_d = p + n * (2L * Ds + Da + 1) + srow;
+  for (int j = lane; j < Ds; j += 64) {
+    states[drow * Ds + j] = p_s[j];
+    next_states[drow * Ds + j] = p_ns[j];
+  }
+  for (int j = lane; j < Da; j += 64)
+    actions[drow * Da + j] = p_a[j];
+  if (lane == 0) {
+    rewards[drow] = p_r[0];
+    dones[drow] = p_d[0];
+  }
+}
+
+// ---------------------------------------------------------------------------
 // K4: fused tanh-squashed Gaussian sample + log-prob (fwd + bwd).
 // One thread per batch row; A = action_dim <= 32.
 // ---------------------------------------------------------------------------
@@ -1791,6 +1846,76 @@ static std::vector<torch::Tensor> replay_sample(
   return {o_s, o_a, o_r, o_ns, o_d};
 }
 
+// Packed ingest: `header` is the HOST copy of the batch (at least its
+// header words), `staging` the device copy the kernel reads.  Every
+// descriptor is re-validated here so a bad one raises on the host and
+// never reaches the kernel.  Returns the number of rows scattered.
+static long replay_ingest(torch::Tensor staging, torch::Tensor header,
+                          torch::Tensor states, torch::Tensor actions,
+                          torch::Tensor rewards, torch::Tensor next_states,
+                          torch::Tensor dones, torch::Tensor sizes) {
+  CHECK_IN(staging); CHECK_IN(states); CHECK_IN(actions); CHECK_IN(rewards);
+  CHECK_IN(next_states); CHECK_IN(dones); CHECK_IN(sizes);
+  TORCH_CHECK(header.device().is_cpu() &&
+                  header.scalar_type() == torch::kFloat32 &&
+                  header.is_contiguous() && staging.is_contiguous(),
+              "header must be a contiguous fp32 host tensor");
+  TORCH_CHECK(states.is_contiguous() && actions.is_contiguous() &&
+                  rewards.is_contiguous() && next_states.is_contiguous() &&
+                  dones.is_contiguous() && sizes.is_contiguous(),
+              "replay fields must be contiguous");
+  TORCH_CHECK(states.dim() == 3 && actions.dim() == 3, "fields are [T,cap,D]");
+  const long T = states.size(0), cap = states.size(1);
+  const long Ds = states.size(2), Da = actions.size(2);
+  TORCH_CHECK(actions.size(0) == T && actions.size(1) == cap &&
+                  rewards.numel() == T * cap && dones.numel() == T * cap &&
+                  next_states.numel() == T * cap * Ds && sizes.numel() == T,
+              "replay field shapes disagree");
+  const long hn = header.numel();
+  TORCH_CHECK(hn >= PK_HDR + T, "packed header truncated");
+  const int32_t* h = reinterpret_cast<const int32_t*>(
+      header.data_ptr<float>());
+  const long n_desc = h[0], total_rows = h[2], used = h[3];
+  TORCH_CHECK(h[1] == T, "packed batch built for another task count");
+  TORCH_CHECK(n_desc >= 1 && PK_HDR + T + n_desc * PK_DESC <= hn,
+              "packed descriptor count out of range");
+  const long pay0 = PK_HDR + T + n_desc * PK_DESC;
+  TORCH_CHECK(used >= pay0 && used <= staging.numel(),
+              "packed batch larger than the staging buffer");
+  const float* hs = header.data_ptr<float>() + PK_HDR;
+  for (long t = 0; t < T; ++t)
+    TORCH_CHECK(hs[t] >= 0.f && hs[t] <= (float)cap,
+                "packed size outside [0, cap]");
+  std::vector<long> per_task(T, 0);
+  long base = 0;
+  for (long k = 0; k < n_desc; ++k) {
+    const int32_t* d = h + PK_HDR + T + k * PK_DESC;
+    const long task = d[0], n = d[1], first = d[2], rows = d[3];
+    const long off = d[4], dst = d[5];
+    TORCH_CHECK(task >= 0 && task < T, "packed descriptor: task out of range");
+    TORCH_CHECK(n >= 1 && rows >= 1 && rows <= cap && first >= 0 &&
+                    first + rows <= n,
+                "packed descriptor: rows out of range");
+    TORCH_CHECK(off >= pay0 && off + n * (2 * Ds + Da + 2) <= used,
+                "packed descriptor: payload outside the staging buffer");
+    TORCH_CHECK(dst >= 0 && dst < cap, "packed descriptor: bad dst row");
+    TORCH_CHECK(d[6] == base, "packed descriptor: bad row_base");
+    base += rows;
+    per_task[task] += rows;
+    TORCH_CHECK(per_task[task] <= cap,
+                "packed batch aliases rows of one task (rows > cap)");
+  }
+  TORCH_CHECK(base == total_rows, "packed row total disagrees");
+  hipLaunchKernelGGL(k_replay_ingest, dim3((total_rows + 3) / 4), dim3(256),
+                     0, cur_stream(), staging.data_ptr<float>(),
+                     states.data_ptr<float>(), actions.data_ptr<float>(),
+                     rewards.data_ptr<float>(),
+                     next_states.data_ptr<float>(), dones.data_ptr<float>(),
+                     sizes.data_ptr<float>(), (int)n_desc, (int)total_rows,
+                     (int)T, cap, (int)Ds, (int)Da);
+  return total_rows;
+}
+
 static std::vector<torch::Tensor> squashed_gaussian_fwd(
     torch::Tensor mu, torch::Tensor lsr, torch::Tensor eps, double k,
     c10::optional<torch::Tensor> rng = c10::nullopt) {
@@ -2379,6 +2504,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           pybind11::arg("dones"), pybind11::arg("sizes"),
           pybind11::arg("rnd"), pybind11::arg("B"),
           pybind11::arg("rng") = pybind11::none());
+  mod.def("replay_ingest", &replay_ingest, "packed replay scatter",
+          pybind11::arg("staging"), pybind11::arg("header"),
+          pybind11::arg("states"), pybind11::arg("actions"),
+          pybind11::arg("rewards"), pybind11::arg("next_states"),
+          pybind11::arg("dones"), pybind11::arg("sizes"));
   mod.def("squashed_gaussian_fwd", &squashed_gaussian_fwd,
           pybind11::arg("mu"), pybind11::arg("lsr"),
           pybind11::arg("eps"), pybind11::arg("k"),

@@ -17,6 +17,8 @@
 #include <cstring>
 #include <string>
 #include <stdexcept>
+#include <tuple>
+#include <vector>
 
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -190,6 +192,54 @@ class ShmRing {
     return {t, s, a, r, ns, d};
   }
 
+  // consumer: drains up to max_blocks pending slots back to back into a
+  // caller-supplied float32 host tensor, starting at float_offset.  Each
+  // payload keeps the slot layout (states|actions|rewards|next_states|
+  // dones for n rows).  Returns one (task, n, offset_in_floats) per block.
+  // Stops WITHOUT consuming a block that does not fit the remaining
+  // staging space, or (when row_budget is given) whose ingested rows
+  // min(n, cap) exceed its task's remaining budget — that block stays
+  // pending.  Allocates no tensors.
+  std::vector<std::tuple<int64_t, int64_t, int64_t>> pop_into(
+      torch::Tensor staging, int64_t float_offset, int64_t max_blocks,
+      std::vector<int64_t> row_budget, int64_t cap) {
+    TORCH_CHECK(staging.device().is_cpu() &&
+                    staging.scalar_type() == torch::kFloat32 &&
+                    staging.is_contiguous(),
+                "staging must be a contiguous float32 host tensor");
+    const int64_t total = staging.numel();
+    TORCH_CHECK(float_offset >= 0 && float_offset <= total,
+                "float_offset outside the staging tensor");
+    std::vector<std::tuple<int64_t, int64_t, int64_t>> out;
+    float* dst = staging.data_ptr<float>();
+    const int64_t Ds = hdr_->state_dim, Da = hdr_->action_dim;
+    uint64_t tail = hdr_->tail.load(std::memory_order_relaxed);
+    const uint64_t head = hdr_->head.load(std::memory_order_acquire);
+    int64_t off = float_offset;
+    for (int64_t k = 0; k < max_blocks && tail != head; ++k) {
+      auto* slot = (Slot*)(slots_ + slot_bytes_ * (tail % hdr_->n_slots));
+      const int64_t n = slot->n;
+      const int64_t task = slot->task;
+      const int64_t need = n * (2 * Ds + Da + 2);
+      TORCH_CHECK(need <= (int64_t)hdr_->slot_floats,
+                  "corrupt ring slot: row count exceeds the slot size");
+      if (off + need > total) break;
+      if (!row_budget.empty() && task < (int64_t)row_budget.size()) {
+        const int64_t rows = (cap > 0 && n > cap) ? cap : n;
+        if (rows > row_budget[task]) break;
+        row_budget[task] -= rows;
+      }
+      std::memcpy(dst + off, (const float*)(slot + 1), (size_t)need * 4);
+      out.emplace_back(task, n, off);
+      off += need;
+      ++tail;
+      hdr_->tail.store(tail, std::memory_order_release);
+    }
+    return out;
+  }
+
+  int64_t slot_floats() const { return hdr_->slot_floats; }
+
  private:
   std::string name_;
   bool owner_;
@@ -219,6 +269,11 @@ void register_shm_ring(pybind11::module_& m) {
       })
       .def("push", &ShmRing::push)
       .def("pop", &ShmRing::pop, pybind11::arg("pinned") = false)
+      .def("pop_into", &ShmRing::pop_into, py::arg("staging"),
+           py::arg("float_offset"), py::arg("max_blocks"),
+           py::arg("row_budget") = std::vector<int64_t>(),
+           py::arg("cap") = 0)
+      .def("slot_floats", &ShmRing::slot_floats)
       .def("pin", &ShmRing::pin)
       .def("pending", &ShmRing::pending)
       .def("capacity", &ShmRing::capacity)

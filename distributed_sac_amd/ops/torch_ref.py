@@ -146,3 +146,97 @@ def attention_pool(z_encs: torch.Tensor, logits: torch.Tensor) -> torch.Tensor:
     """
     alpha = F.softmax(logits, dim=-1)
     return (z_encs * alpha.unsqueeze(-1)).sum(dim=1)
+
+
+# ---------------------------------------------------------------------------
+# Packed replay ingest (docs/KERNELS.md "packed replay batch"): CPU path and
+# oracle of the k_replay_ingest scatter kernel.
+# ---------------------------------------------------------------------------
+
+PK_HDR = 4    # header words: n_desc, T, total_rows, used
+PK_DESC = 8   # words per descriptor:
+#               task, n, first, rows, offset, dst_row, row_base, 0
+
+
+def packed_header_words(num_tasks: int, max_desc: int) -> int:
+    """Words reserved in front of the payloads for ``max_desc`` blocks."""
+    return PK_HDR + num_tasks + PK_DESC * max_desc
+
+
+def packed_validate(packed: torch.Tensor, num_tasks: int, cap: int,
+                    state_dim: int, action_dim: int) -> list:
+    """Check every header field of a packed batch against the replay
+    geometry and the buffer's own extent; returns the descriptors as
+    rows of ints.  Raises ``ValueError`` on the first bad field — a bad
+    descriptor must never reach a scatter."""
+    if packed.device.type != "cpu" or packed.dtype != torch.float32 \
+            or packed.dim() != 1 or not packed.is_contiguous():
+        raise ValueError("packed batch must be a flat fp32 host tensor")
+    T = num_tasks
+    if packed.numel() < PK_HDR + T:
+        raise ValueError("packed header truncated")
+    h = packed.view(torch.int32)
+    n_desc, t_hdr, total_rows, used = h[:PK_HDR].tolist()
+    if t_hdr != T:
+        raise ValueError("packed batch built for another task count")
+    pay0 = PK_HDR + T + PK_DESC * n_desc
+    if n_desc < 1 or pay0 > packed.numel():
+        raise ValueError("packed descriptor count out of range")
+    if used < pay0 or used > packed.numel():
+        raise ValueError("packed batch larger than the staging buffer")
+    for s in packed[PK_HDR:PK_HDR + T].tolist():
+        if not 0.0 <= s <= float(cap):
+            raise ValueError("packed size outside [0, cap]")
+    descs = h[PK_HDR + T:pay0].reshape(n_desc, PK_DESC).tolist()
+    row_floats = 2 * state_dim + action_dim + 2
+    per_task = [0] * T
+    base = 0
+    for task, n, first, rows, off, dst, row_base, _ in descs:
+        if not 0 <= task < T:
+            raise ValueError("packed descriptor: task out of range")
+        if n < 1 or rows < 1 or rows > cap or first < 0 or first + rows > n:
+            raise ValueError("packed descriptor: rows out of range")
+        if off < pay0 or off + n * row_floats > used:
+            raise ValueError(
+                "packed descriptor: payload outside the staging buffer")
+        if not 0 <= dst < cap:
+            raise ValueError("packed descriptor: bad dst row")
+        if row_base != base:
+            raise ValueError("packed descriptor: bad row_base")
+        base += rows
+        per_task[task] += rows
+        if per_task[task] > cap:
+            raise ValueError(
+                "packed batch aliases rows of one task (rows > cap)")
+    if base != total_rows:
+        raise ValueError("packed row total disagrees")
+    return descs
+
+
+@torch.no_grad()
+def replay_ingest(packed: torch.Tensor, states: torch.Tensor,
+                  actions: torch.Tensor, rewards: torch.Tensor,
+                  next_states: torch.Tensor, dones: torch.Tensor,
+                  sizes: torch.Tensor) -> int:
+    """Decode one packed batch into the ``[T, cap, D]`` field tensors and
+    the per-task ``sizes``.  Validates first (nothing is written when a
+    descriptor is bad).  Returns the number of rows written."""
+    T, cap, Ds = states.shape
+    Da = actions.shape[2]
+    descs = packed_validate(packed, T, cap, Ds, Da)
+    total = 0
+    for task, n, first, rows, off, dst, _base, _ in descs:
+        p = packed[off:off + n * (2 * Ds + Da + 2)]
+        o = 0
+        src = []
+        for w in (Ds, Da, 1, Ds, 1):
+            src.append(p[o:o + n * w].reshape(n, w)[first:first + rows])
+            o += n * w
+        idx = (torch.arange(rows) + dst) % cap
+        for field, s in zip((states, actions, rewards, next_states, dones),
+                            src):
+            field[task].index_copy_(0, idx.to(field.device),
+                                    s.to(field.device))
+        total += rows
+    sizes.copy_(packed[PK_HDR:PK_HDR + T])
+    return total

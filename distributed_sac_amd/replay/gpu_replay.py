@@ -11,7 +11,11 @@ MT10_Distributed_MTSAC/src/replay_buffers.py:13-107 per-task deques):
   np.vstack + torch.from_numpy().to(device) per update).
 - Ingest crosses the PCIe/host boundary once, batched: numpy transition
   blocks are staged into a reusable pinned buffer and copied with one
-  async H2D per field (overlappable with the update stream).
+  async H2D per field (overlappable with the update stream).  Ring blocks
+  can instead take the packed path (``stage_packed`` / ``commit_packed``
+  / ``flush_packed``): a whole drain is packed into one pinned staging
+  buffer, copied H2D once on a copy stream and scattered into the shards
+  by one ``k_replay_ingest`` launch on the main stream.
 - MT variants shard per task with stratified sampling (batch//num_tasks
   from each shard, shuffled concat) and ``len = min over shards`` —
   reference replay_buffers.py:37-41,67-100 semantics.
@@ -129,6 +133,38 @@ class ReplayShard:
         return self.gather(self.sample_indices(n, generator, graph_safe))
 
 
+class _StagingPair:
+    """One host (pinned on GPU) + device staging buffer of the packed
+    ingest path.  On CPU both names refer to the same tensor."""
+
+    def __init__(self, floats: int, device: torch.device):
+        cuda = device.type == "cuda"
+        self.host = torch.zeros(floats, pin_memory=cuda)
+        self.host_i32 = self.host.view(torch.int32)
+        self.dev = torch.empty(floats, device=device) if cuda else self.host
+        self.copy_event = torch.cuda.Event() if cuda else None
+        self.done_event = torch.cuda.Event() if cuda else None
+        self.free = True          # False from stage until its scatter is done
+        self.scattered = False    # scatter launched, done_event recorded
+
+
+class _PackedBatch:
+    """Host-side bookkeeping of one packed batch being built/in flight."""
+
+    def __init__(self, pair: _StagingPair, off: int, num_tasks: int,
+                 wp0: List[int], size0: List[int]):
+        self.pair = pair
+        self.off = off            # float cursor: end of the staged payloads
+        self.desc: List[int] = []
+        self.n_desc = 0
+        self.rows = 0
+        self.rows_t = [0] * num_tasks
+        self.wp0, self.size0 = wp0, size0   # restored if the build aborts
+        self.post_wp: List[int] = []
+        self.post_size: List[int] = []
+        self.used = 0
+
+
 class ShardedReplay:
     """Per-task shards + stratified sampling (MT semantics) with a pinned
     staging path for host-produced transitions.
@@ -166,6 +202,19 @@ class ShardedReplay:
             self.generator.manual_seed(seed)
         self._rng_ctr = None     # optional int64 counter (attach_rng)
         self._empty_rnd = None
+        # packed ingest (stage_packed / commit_packed / flush_packed):
+        # staging pairs are allocated at first use
+        self._pk_pairs: List[_StagingPair] = []
+        self._pk_pending: List[_PackedBatch] = []   # staged, not committed
+        self._pk_copy_stream = None
+        self._pk_max_desc = 0
+        self.packed_batches = 0   # batches committed so far
+        self._pk_hdr_words = 0
+        self._pk_open_batch: Optional[_PackedBatch] = None
+        # write pointers / sizes as of the last STAGED batch; the shards'
+        # own write_ptr/size follow at commit
+        self._pk_wp = [0] * num_tasks
+        self._pk_size = [0] * num_tasks
 
     def attach_rng(self, ctr: torch.Tensor) -> None:
         """Use the engine's counter-based device RNG for graph-safe
@@ -192,10 +241,264 @@ class ShardedReplay:
             return t.pin_memory().to(self.device, non_blocking=True)
         return t
 
+    # -- packed ingest ---------------------------------------------------
+    # One H2D copy + one scatter launch per batch of blocks (format:
+    # docs/KERNELS.md "packed replay batch").  stage_packed() packs blocks
+    # into a free staging pair and starts its copy on a dedicated stream;
+    # commit_packed() launches the scatter ON THE CURRENT (main) STREAM for
+    # batches whose copy already finished, so the main stream never waits
+    # for PCIe and the scatter is ordered against the sampler like the
+    # per-block slice copies.  Host-visible size/write_ptr/len() change at
+    # commit.  append/append_numpy/sample flush pending batches first.
+
+    @property
+    def _row_floats(self) -> int:
+        return 2 * self.f_states.shape[2] + self.f_actions.shape[2] + 2
+
+    def configure_packed(self, payload_floats: int, max_desc: int = 256,
+                         pairs: int = 4) -> None:
+        """(Re)allocate the staging pairs: ``pairs`` (>= 2) buffers holding
+        up to ``max_desc`` blocks / ``payload_floats`` payload floats per
+        batch.  Called with defaults at first use; flushes first."""
+        from ..ops import torch_ref
+        self.flush_packed()
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)  # no scatter reads old pairs
+            if self._pk_copy_stream is None:
+                self._pk_copy_stream = torch.cuda.Stream(self.device)
+        self._pk_max_desc = int(max_desc)
+        self._pk_hdr_words = torch_ref.packed_header_words(
+            self.num_tasks, self._pk_max_desc)
+        floats = self._pk_hdr_words + int(payload_floats)
+        self._pk_pairs = [_StagingPair(floats, self.device)
+                          for _ in range(max(2, int(pairs)))]
+
+    def pending_packed(self) -> List[torch.Tensor]:
+        """Host views (header + payloads) of the staged, uncommitted
+        batches, oldest first."""
+        return [b.pair.host[:b.used] for b in self._pk_pending]
+
+    def _pk_open(self) -> Optional[_PackedBatch]:
+        for p in self._pk_pairs:
+            if not p.free and p.scattered and p.done_event.query():
+                p.free, p.scattered = True, False
+        for p in self._pk_pairs:
+            if p.free:
+                p.free = False
+                return _PackedBatch(p, self._pk_hdr_words, self.num_tasks,
+                                    list(self._pk_wp), list(self._pk_size))
+        return None
+
+    def _pk_abort(self, b: _PackedBatch) -> None:
+        self._pk_wp, self._pk_size = b.wp0, b.size0
+        b.pair.free = True
+
+    def _pk_add(self, b: _PackedBatch, task: int, n: int, off: int) -> None:
+        """Descriptor for one staged block: assigns its write pointer."""
+        cap = self.shards[0].capacity
+        if not 0 <= task < self.num_tasks:
+            raise ValueError(f"packed block: task {task} out of range "
+                             f"[0, {self.num_tasks})")
+        rows = min(n, cap)        # keep only the newest `capacity` rows
+        dst = self._pk_wp[task]
+        b.desc += (task, n, n - rows, rows, off, dst, b.rows, 0)
+        b.n_desc += 1
+        b.rows += rows
+        b.rows_t[task] += rows
+        self._pk_wp[task] = (dst + rows) % cap
+        self._pk_size[task] = min(self._pk_size[task] + rows, cap)
+
+    def _pk_close(self, b: _PackedBatch) -> None:
+        """Write the header and start the H2D copy on the copy stream."""
+        from ..ops import torch_ref
+        if b.n_desc == 0:
+            b.pair.free = True
+            return
+        T, pair = self.num_tasks, b.pair
+        b.used = b.off
+        b.post_wp, b.post_size = list(self._pk_wp), list(self._pk_size)
+        h0 = torch_ref.PK_HDR
+        pair.host_i32[:h0] = torch.tensor([b.n_desc, T, b.rows, b.used],
+                                          dtype=torch.int32)
+        pair.host[h0:h0 + T] = torch.tensor(b.post_size, dtype=torch.float32)
+        pair.host_i32[h0 + T:h0 + T + len(b.desc)] = torch.tensor(
+            b.desc, dtype=torch.int32)
+        if self.device.type == "cuda":
+            with torch.cuda.stream(self._pk_copy_stream):
+                pair.dev[:b.used].copy_(pair.host[:b.used], non_blocking=True)
+                pair.copy_event.record(self._pk_copy_stream)
+        self._pk_pending.append(b)
+
+    @torch.no_grad()
+    def stage_packed(self, rings=None, blocks=None,
+                     max_blocks: int = 64) -> int:
+        """Pack pending blocks into staging pairs and start their H2D
+        copies.  Give either ``rings`` (native ShmRing objects; up to
+        ``max_blocks`` per ring are drained with ``pop_into``) or ``blocks``
+        (an iterable of ``(task, states, actions, rewards, next_states,
+        dones)`` host tensors).  A new batch starts whenever a pair fills
+        or one task's rows in the batch would exceed the shard capacity
+        (no two rows of one launch share a destination).  Stops when no
+        pair is free — unstaged blocks stay in their ring / with the
+        caller.  Returns the number of blocks taken."""
+        if (rings is None) == (blocks is None):
+            raise ValueError("give exactly one of rings= / blocks=")
+        if blocks is not None:
+            blocks = list(blocks)
+            for blk in blocks:   # reject bad input before any packing
+                if not 0 <= int(blk[0]) < self.num_tasks:
+                    raise ValueError(f"packed block: task {int(blk[0])} out "
+                                     f"of range [0, {self.num_tasks})")
+        if not self._pk_pairs:
+            if rings is not None:
+                slot = max((int(r.slot_floats()) for r in rings), default=0)
+                self.configure_packed(max(slot, min(256 * slot, 1 << 23)))
+            else:
+                need = max((b[1].shape[0] for b in blocks), default=0)
+                self.configure_packed(max(1 << 16,
+                                          4 * need * self._row_floats))
+        if not self._pk_pending:   # shards may have moved via append()
+            self._pk_wp = [s.write_ptr for s in self.shards]
+            self._pk_size = [s.size for s in self.shards]
+        b: Optional[_PackedBatch] = None
+        taken = 0
+        try:
+            if blocks is not None:
+                taken, b = self._pk_stage_blocks(blocks)
+            else:
+                taken, b = self._pk_stage_rings(rings, max_blocks)
+        except BaseException:
+            # roll the staged-view pointers back to the last closed batch
+            if self._pk_open_batch is not None:
+                self._pk_abort(self._pk_open_batch)
+                self._pk_open_batch = None
+            raise
+        if b is not None:
+            self._pk_close(b)
+        self._pk_open_batch = None
+        return taken
+
+    def _pk_stage_blocks(self, blocks):
+        cap, rf = self.shards[0].capacity, self._row_floats
+        limit = self._pk_pairs[0].host.numel()
+        Ds, Da = self.f_states.shape[2], self.f_actions.shape[2]
+        b, taken = None, 0
+        for task, s, a, r, ns, d in blocks:
+            task, n = int(task), s.shape[0]
+            if n == 0:
+                taken += 1
+                continue
+            need = n * rf
+            if self._pk_hdr_words + need > limit:
+                raise ValueError("packed block larger than a staging buffer")
+            if b is not None and (b.off + need > limit
+                                  or b.n_desc >= self._pk_max_desc
+                                  or b.rows_t[task] + min(n, cap) > cap):
+                self._pk_close(b)
+                b = self._pk_open_batch = None
+            if b is None:
+                b = self._pk_open_batch = self._pk_open()
+                if b is None:
+                    break
+            o = b.off
+            for src, w in ((s, Ds), (a, Da), (r, 1), (ns, Ds), (d, 1)):
+                b.pair.host[o:o + n * w].copy_(src.reshape(-1))
+                o += n * w
+            self._pk_add(b, task, n, b.off)
+            b.off = o
+            taken += 1
+        return taken, b
+
+    def _pk_stage_rings(self, rings, max_blocks):
+        cap, rf = self.shards[0].capacity, self._row_floats
+        b, taken = None, 0
+        for ring in rings:
+            left = max_blocks
+            while left > 0:
+                pend = int(ring.pending())
+                if pend == 0:
+                    break
+                if b is None:
+                    b = self._pk_open_batch = self._pk_open()
+                    if b is None:
+                        return taken, None
+                k = min(left, pend, self._pk_max_desc - b.n_desc)
+                got = ring.pop_into(b.pair.host, b.off, k,
+                                    [cap - x for x in b.rows_t], cap) \
+                    if k > 0 else []
+                for task, n, off in got:
+                    b.off = off + n * rf
+                    if n:
+                        self._pk_add(b, task, n, off)
+                taken += len(got)
+                left -= len(got)
+                if len(got) < k or k <= 0:
+                    # the next block did not fit this batch (space,
+                    # descriptor count or its task's row budget)
+                    if not got and b.off == self._pk_hdr_words:
+                        raise RuntimeError(
+                            "ring block larger than a staging buffer")
+                    self._pk_close(b)
+                    b = self._pk_open_batch = None
+        return taken, b
+
+    def _pk_scatter(self, b: _PackedBatch) -> None:
+        from ..ops import native, native_enabled, torch_ref
+        pair = b.pair
+        fields = (self.f_states, self.f_actions, self.f_rewards,
+                  self.f_next_states, self.f_dones, self.sizes_dev)
+        if self.device.type == "cuda" and native_enabled():
+            # host re-validation + launch on the current (main) stream
+            native().replay_ingest(pair.dev, pair.host[:self._pk_hdr_words],
+                                   *fields)
+            pair.done_event.record()
+            pair.scattered = True
+        else:
+            torch_ref.replay_ingest(pair.host[:b.used], *fields)
+            pair.free = True
+        for t, shard in enumerate(self.shards):
+            shard.write_ptr, shard.size = b.post_wp[t], b.post_size[t]
+
+    @torch.no_grad()
+    def commit_packed(self) -> int:
+        """Launch the scatter for every staged batch whose H2D copy has
+        completed (in order; a batch still copying blocks the ones behind
+        it until the next call).  Returns the rows committed."""
+        rows = 0
+        while self._pk_pending:
+            b = self._pk_pending[0]
+            if b.pair.copy_event is not None \
+                    and not b.pair.copy_event.query():
+                break
+            try:
+                self._pk_scatter(b)
+            except BaseException:
+                # a rejected batch poisons everything staged behind it
+                for x in self._pk_pending:
+                    x.pair.free = True
+                self._pk_pending.clear()
+                raise
+            self._pk_pending.pop(0)
+            rows += b.rows
+            self.packed_batches += 1
+        return rows
+
+    @torch.no_grad()
+    def flush_packed(self) -> int:
+        """Wait for every pending batch's copy and commit it."""
+        rows = 0
+        while self._pk_pending:
+            ev = self._pk_pending[0].pair.copy_event
+            if ev is not None:
+                ev.synchronize()
+            rows += self.commit_packed()
+        return rows
+
     @torch.no_grad()
     def append_numpy(self, states, actions, rewards, next_states, dones,
                      task_idx: int = 0) -> None:
         """Ingest a block of host transitions into one task shard."""
+        self.flush_packed()
         s = self._stage("s", states)
         a = self._stage("a", actions)
         r = self._stage("r", np.asarray(rewards).reshape(-1, 1))
@@ -205,6 +508,7 @@ class ShardedReplay:
 
     @torch.no_grad()
     def append(self, task_idx: int, **fields: torch.Tensor) -> None:
+        self.flush_packed()
         self.shards[task_idx].append(
             fields["states"], fields["actions"], fields["rewards"],
             fields["next_states"], fields["dones"])
@@ -217,7 +521,12 @@ class ShardedReplay:
 
         graph_safe=True uses the hipGraph-capturable index draw and skips
         the concat shuffle (every consumer of the batch is
-        permutation-invariant: all losses are batch means)."""
+        permutation-invariant: all losses are batch means).
+
+        Pending packed batches are flushed first, so the host-side sizes
+        the non-graph draw uses match what is in device memory."""
+        if self._pk_pending:
+            self.flush_packed()
         gen = None if graph_safe else self.generator
         if graph_safe and self.device.type == "cuda":
             from ..ops import has_native, native, native_enabled

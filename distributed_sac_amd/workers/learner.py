@@ -44,7 +44,7 @@ class Learner:
                  ddp=None, seed: int = 0, heartbeat=None,
                  heartbeat_timeout: float = 60.0, rings=None,
                  precision: str = None, publish_interval_s: float = 0.02,
-                 graph_chunk: int = 4):
+                 graph_chunk: int = 4, ingest: Optional[str] = None):
         self.cfg = cfg
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -64,6 +64,15 @@ class Learner:
         self.snapshot = snapshot
         self.sample_queue = sample_queue
         self.rings = rings or []
+        # ring ingest path: "blocks" = one pop + five slice copies per
+        # block (default); "packed" = one staging buffer, one H2D copy on
+        # a copy stream and one k_replay_ingest scatter per drain
+        if ingest is None:
+            ingest = os.environ.get("DSAC_INGEST", "blocks")
+        if ingest not in ("blocks", "packed"):
+            raise ValueError(f"ingest must be 'blocks' or 'packed', "
+                             f"got {ingest!r}")
+        self.ingest = ingest
         if self.rings and self.device.type == "cuda":
             for r in self.rings:
                 r.pin()  # hipHostRegister: DMA-able drains
@@ -162,6 +171,14 @@ class Learner:
     # -- ingest --------------------------------------------------------
     def drain_rings(self, max_blocks: int = 64) -> int:
         """Drain the native shared-memory SPSC rings (one per player)."""
+        if self.ingest == "packed":
+            if not self.rings:
+                return 0
+            # scatter the batches whose copy finished since the last tick,
+            # then stage what is pending now (its copy overlaps the update)
+            self._count_ingested(self.replay.commit_packed())
+            return self.replay.stage_packed(rings=self.rings,
+                                            max_blocks=max_blocks)
         n = 0
         pinned = self.device.type == "cuda"
         for ring in self.rings:
@@ -179,6 +196,15 @@ class Learner:
                 self.ingest_count += got
                 n += 1
         return n
+
+    def _count_ingested(self, rows: int) -> None:
+        self.engine.total_step += rows
+        self.ingest_count += rows
+
+    def flush_packed(self) -> None:
+        """Commit every staged packed batch (waits for its H2D copy)."""
+        if self.ingest == "packed":
+            self._count_ingested(self.replay.flush_packed())
 
     def drain_queue(self, max_blocks: int = 64) -> int:
         n = self.drain_rings(max_blocks)
@@ -292,6 +318,9 @@ class Learner:
                                     self.replay.shards[0].capacity)
 
     def _ensure_graph(self) -> None:
+        if not (self._graph_ready or self._dp_graph_ready):
+            # capture calls replay.sample(); no event wait may fall inside
+            self.flush_packed()
         if self.use_graph and not self._graph_ready:
             try:
                 self.logger.print("capturing update graph...")
@@ -392,6 +421,7 @@ class Learner:
             if stop_event is not None and stop_event.is_set():
                 return {}
             self.drain_queue()
+            self.flush_packed()   # ready() only sees committed rows
             self.drain_logs()
             time.sleep(0.01)
             if max_seconds and time.perf_counter() - t0 > max_seconds:
@@ -425,6 +455,7 @@ class Learner:
                 break
             if max_seconds and time.perf_counter() - t0 > max_seconds:
                 break
+        self.flush_packed()   # no popped block is lost
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)  # completion-accurate rate
             # flush any in-flight async publish so players/evaluators see
