@@ -94,6 +94,11 @@ class SACConfig:
     # broadcast where the weights cancel (= mean(loss)/B) — strict-parity
     # mode, CPU torch path only.  See docs/PARITY.md "weighted loss".
     weighted_loss_mode: str = "corrected"
+    # "replace" (default; a cfg without the key): minibatch rows drawn
+    # independently.  "without_replacement": each shard's rows of a batch
+    # are distinct, as the reference's random.sample.  See docs/PARITY.md
+    # "replay sampling".
+    replay_sampling: str = "replace"
     # CARE-only block (reference cfg "encoder"):
     encoder: Optional[Dict[str, Any]] = None
     use_modified_care: bool = False
@@ -108,6 +113,16 @@ class SACConfig:
         if self.variant in ("mtsac", "care"):
             return self.state_dim + self.num_tasks
         return self.state_dim
+
+    @property
+    def replay_sampling_choice(self) -> Optional[str]:
+        """``replay_sampling`` if this cfg chose it (the key is in the raw
+        dict, or the field was changed from its default), else None: the
+        replay then takes its own default (``DSAC_SAMPLING``, else
+        ``replace``)."""
+        if "replay_sampling" in self.raw or self.replay_sampling != "replace":
+            return self.replay_sampling
+        return None
 
     @property
     def k(self) -> float:
@@ -150,6 +165,12 @@ class SACConfig:
             c.use_weighted_loss = bool(cfg["use_weighted_loss"])
         if "weighted_loss_mode" in cfg:
             c.weighted_loss_mode = str(cfg["weighted_loss_mode"])
+        if "replay_sampling" in cfg:
+            c.replay_sampling = str(cfg["replay_sampling"])
+            if c.replay_sampling not in ("replace", "without_replacement"):
+                raise ValueError(
+                    "replay_sampling must be 'replace' or "
+                    f"'without_replacement', got {c.replay_sampling!r}")
         if "use_modified_care" in cfg:
             c.use_modified_care = bool(cfg["use_modified_care"])
         if "encoder" in cfg:

@@ -43,6 +43,10 @@ def main():
                          "(default: 40 for Meta-World variants, 0 for LL)")
     ap.add_argument("--env", default=None,
                     help="env name for make_env (default: synthetic)")
+    ap.add_argument("--sampling", default=None,
+                    choices=["replace", "without_replacement"],
+                    help="replay minibatch draw (default: the cfg's "
+                         "replay_sampling, else DSAC_SAMPLING, else replace)")
     # eval mode
     ap.add_argument("--eval", action="store_true")
     ap.add_argument("--checkpoint", default=None)
@@ -104,7 +108,8 @@ def main():
                             save_period=args.save_period, seed=args.seed,
                             use_graph=not args.no_graph, ddp=ddp,
                             precision=args.precision,
-                            eval_every_episodes=args.eval_every)
+                            eval_every_episodes=args.eval_every,
+                            sampling=args.sampling)
     stats = dt.run(max_grad_steps=args.max_grad_steps,
                    max_seconds=args.max_seconds)
     print(json.dumps(stats))

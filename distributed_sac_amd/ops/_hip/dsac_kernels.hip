@@ -16,6 +16,8 @@
 //   K10 polyak_              — fused soft target update over flat buffers
 //   K12 replay_sample        — stratified gather from the HBM-resident
 //                              sharded replay in ONE kernel
+//       replay_sample_norepl — the same gather drawing without replacement
+//                              (keyed permutation evaluated per row)
 //
 // Design notes (see /opt/skills guides):
 // - fp32 end-to-end like the reference; GEMMs use the exact f32-input MFMA
@@ -429,6 +431,93 @@ __global__ __launch_bounds__(256) void k_replay_sample(
   if (lane == 0) {
     o_rewards[i] = rewards[src];
     o_dones[i] = dones[src];
+  }
+}
+
+// ---------------------------------------------------------------------------
+// K12c: stratified replay sample WITHOUT replacement (opt-in; the
+// reference's random.sample semantics).  Row j of shard t (size n, read on
+// the device) gathers index (P(j mod n) + rot) mod n, where P is a keyed
+// bijection of [0, n) and rot a keyed offset (docs/KERNELS.md "replay
+// permutation"; the exact oracle is torch_ref.replay_sample_indices_norepl).
+// P: NR_ROUNDS alternating unbalanced XOR-Feistel rounds over
+// b = max(6, ceil(log2 n)) bits (low half b/2 bits, high half the rest),
+// cycle-walked while the value is >= n.  The walk stays on one cycle of a
+// bijection of [0, 2^b) that contains the start value (< n), so it returns
+// below n after at most 2^b - n + 1 applications — the loop has no cap, a
+// cap would break bijectivity.
+//
+// Key = dsac_sm64(c * 0x100000001 + 2^63 + t).  k_replay_sample hashes
+// c * 0x100000001 + 2 i + 2 and k_squash_fwd hashes c * 0x100000001 + 2 idx
+// + 1, with 2 i + 2 and 2 idx + 1 below 2^32: for counters below 2^31 - 2
+// (the counter starts below 2^31 and grows by one per update) those hash
+// inputs stay below 2^63 and these are at or above it, and dsac_sm64 is a
+// bijection of the 64-bit words, so the key can equal none of their draws'
+// hashes by sharing an input.  Round and offset values hash key + (r << 32)
+// + v, a second hash level the other streams do not have.
+// ---------------------------------------------------------------------------
+constexpr int NR_ROUNDS = 8;
+
+__device__ __forceinline__ unsigned dsac_norepl_index(
+    unsigned long long c, unsigned t, unsigned j, unsigned n) {
+  const unsigned long long key = dsac_sm64(
+      c * 0x100000001ull + 0x8000000000000000ull + (unsigned long long)t);
+  const unsigned rot = (unsigned)(dsac_sm64(key) >> 32) % n;
+  const int b = n <= 64u ? 6 : 32 - __clz((int)(n - 1u));
+  const int bl = b >> 1;
+  const unsigned ml = (1u << bl) - 1u, mh = (1u << (b - bl)) - 1u;
+  unsigned x = j % n;
+  do {
+    unsigned lo = x & ml, hi = x >> bl;
+#pragma unroll
+    for (int r = 0; r < NR_ROUNDS; ++r) {
+      const unsigned long long kr = key + ((unsigned long long)(r + 1) << 32);
+      if ((r & 1) == 0)
+        lo ^= (unsigned)(dsac_sm64(kr + hi) >> 32) & ml;
+      else
+        hi ^= (unsigned)(dsac_sm64(kr + lo) >> 32) & mh;
+    }
+    x = (hi << bl) | lo;
+  } while (x >= n);
+  x += rot;                      // x, rot < n <= 2^31: no wrap
+  return x >= n ? x - n : x;
+}
+
+__global__ __launch_bounds__(256) void k_replay_sample_norepl(
+    const float* __restrict__ states, const float* __restrict__ actions,
+    const float* __restrict__ rewards, const float* __restrict__ next_states,
+    const float* __restrict__ dones, const float* __restrict__ sizes,
+    const long long* __restrict__ rng, float* __restrict__ o_states,
+    float* __restrict__ o_actions, float* __restrict__ o_rewards,
+    float* __restrict__ o_next_states, float* __restrict__ o_dones,
+    long long* __restrict__ idx_out, int B, int T, int per, long cap, int Ds,
+    int Da) {
+  // one wave per batch row, as k_replay_sample.  The row is the same for
+  // all 64 lanes; readfirstlane lets the compiler see that, so the index
+  // (hashes, walk loop) is computed once per wave on the scalar unit and
+  // the loop cannot diverge.
+  const int i = __builtin_amdgcn_readfirstlane(
+      (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));
+  const int lane = threadIdx.x & 63;
+  if (i >= B) return;
+  const int t = min(i / per, T - 1);
+  // an empty shard reads row 0 (n = 1); a size beyond the storage cannot
+  // index past it
+  unsigned n = (unsigned)fmaxf(sizes[t], 1.f);
+  n = (long)n > cap ? (unsigned)cap : n;
+  const long idx = (long)dsac_norepl_index(
+      (unsigned long long)rng[0], (unsigned)t, (unsigned)(i - t * per), n);
+  const long src = (long)t * cap + idx;
+  for (int j = lane; j < Ds; j += 64) {
+    o_states[(long)i * Ds + j] = states[src * Ds + j];
+    o_next_states[(long)i * Ds + j] = next_states[src * Ds + j];
+  }
+  for (int j = lane; j < Da; j += 64)
+    o_actions[(long)i * Da + j] = actions[src * Da + j];
+  if (lane == 0) {
+    o_rewards[i] = rewards[src];
+    o_dones[i] = dones[src];
+    if (idx_out != nullptr) idx_out[i] = idx;
   }
 }
 
@@ -1846,6 +1935,64 @@ static std::vector<torch::Tensor> replay_sample(
   return {o_s, o_a, o_r, o_ns, o_d};
 }
 
+// Without-replacement draw (k_replay_sample_norepl).  `idx_out`, if given,
+// receives the B drawn in-shard indices; the captured update passes none.
+static std::vector<torch::Tensor> replay_sample_norepl(
+    torch::Tensor states, torch::Tensor actions, torch::Tensor rewards,
+    torch::Tensor next_states, torch::Tensor dones, torch::Tensor sizes,
+    long B, torch::Tensor rng,
+    c10::optional<torch::Tensor> idx_out = c10::nullopt) {
+  CHECK_IN(states); CHECK_IN(actions); CHECK_IN(rewards);
+  CHECK_IN(next_states); CHECK_IN(dones); CHECK_IN(sizes);
+  TORCH_CHECK(rng.is_cuda() && rng.scalar_type() == torch::kInt64
+              && rng.numel() >= 1, "rng counter must be an int64 HIP tensor");
+  TORCH_CHECK(states.dim() == 3 && states.is_contiguous(),
+              "states must be a contiguous [T, cap, Ds] tensor");
+  const long T = states.size(0), cap = states.size(1);
+  const long Ds = states.size(2);
+  TORCH_CHECK(T >= 1 && cap >= 1 && cap < (1L << 31),
+              "replay geometry out of range");
+  TORCH_CHECK(actions.dim() == 3 && actions.is_contiguous()
+              && actions.size(0) == T && actions.size(1) == cap,
+              "actions must be a contiguous [T, cap, Da] tensor");
+  const long Da = actions.size(2);
+  TORCH_CHECK(next_states.is_contiguous()
+              && next_states.sizes() == states.sizes(),
+              "next_states must match states");
+  TORCH_CHECK(rewards.is_contiguous() && rewards.numel() == T * cap
+              && dones.is_contiguous() && dones.numel() == T * cap,
+              "rewards/dones must be contiguous [T, cap, 1] tensors");
+  TORCH_CHECK(sizes.is_contiguous() && sizes.numel() == T,
+              "sizes must hold one entry per task");
+  TORCH_CHECK(B >= 1 && B < (1L << 31) && B % T == 0,
+              "batch must be positive and divide by num_tasks");
+  const int per = (int)(B / T);
+  long long* idx_p = nullptr;
+  if (idx_out.has_value()) {
+    TORCH_CHECK(idx_out->is_cuda() && idx_out->scalar_type() == torch::kInt64
+                && idx_out->is_contiguous() && idx_out->numel() == B,
+                "idx_out must be a contiguous int64 HIP tensor of B entries");
+    idx_p = (long long*)idx_out->data_ptr<long>();
+  }
+  auto opt = states.options();
+  auto o_s = torch::empty({B, Ds}, opt);
+  auto o_a = torch::empty({B, Da}, opt);
+  auto o_r = torch::empty({B, 1}, opt);
+  auto o_ns = torch::empty({B, Ds}, opt);
+  auto o_d = torch::empty({B, 1}, opt);
+  hipLaunchKernelGGL(k_replay_sample_norepl, dim3((B + 3) / 4), dim3(256), 0,
+                     cur_stream(), states.data_ptr<float>(),
+                     actions.data_ptr<float>(), rewards.data_ptr<float>(),
+                     next_states.data_ptr<float>(), dones.data_ptr<float>(),
+                     sizes.data_ptr<float>(),
+                     (const long long*)rng.data_ptr<long>(),
+                     o_s.data_ptr<float>(), o_a.data_ptr<float>(),
+                     o_r.data_ptr<float>(), o_ns.data_ptr<float>(),
+                     o_d.data_ptr<float>(), idx_p, (int)B, (int)T, per, cap,
+                     (int)Ds, (int)Da);
+  return {o_s, o_a, o_r, o_ns, o_d};
+}
+
 // Packed ingest: `header` is the HOST copy of the batch (at least its
 // header words), `staging` the device copy the kernel reads.  Every
 // descriptor is re-validated here so a bad one raises on the host and
@@ -2504,6 +2651,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           pybind11::arg("dones"), pybind11::arg("sizes"),
           pybind11::arg("rnd"), pybind11::arg("B"),
           pybind11::arg("rng") = pybind11::none());
+  mod.def("replay_sample_norepl", &replay_sample_norepl,
+          "stratified replay gather, without replacement",
+          pybind11::arg("states"), pybind11::arg("actions"),
+          pybind11::arg("rewards"), pybind11::arg("next_states"),
+          pybind11::arg("dones"), pybind11::arg("sizes"),
+          pybind11::arg("B"), pybind11::arg("rng"),
+          pybind11::arg("idx_out") = pybind11::none());
   mod.def("replay_ingest", &replay_ingest, "packed replay scatter",
           pybind11::arg("staging"), pybind11::arg("header"),
           pybind11::arg("states"), pybind11::arg("actions"),

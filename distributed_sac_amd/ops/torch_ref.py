@@ -240,3 +240,92 @@ def replay_ingest(packed: torch.Tensor, states: torch.Tensor,
         total += rows
     sizes.copy_(packed[PK_HDR:PK_HDR + T])
     return total
+
+
+# ---------------------------------------------------------------------------
+# Without-replacement replay draw (docs/KERNELS.md "replay permutation"): the
+# CPU path and the exact oracle of k_replay_sample_norepl.  Same integer
+# algorithm, in int64 tensors: additions and multiplications wrap like the
+# kernel's uint64, right shifts are made logical by masking.
+# ---------------------------------------------------------------------------
+
+NR_ROUNDS = 8        # Feistel rounds
+NR_MIN_BITS = 6      # floor of the permutation's domain width
+
+
+def _i64(x: int) -> int:
+    """A 64-bit word as the signed Python int with the same bits."""
+    x &= (1 << 64) - 1
+    return x - (1 << 64) if x >= (1 << 63) else x
+
+
+def _lsr(x: torch.Tensor, k: int) -> torch.Tensor:
+    return (x >> k) & ((1 << (64 - k)) - 1)
+
+
+def _sm64(x: torch.Tensor) -> torch.Tensor:
+    """splitmix64 finalizer on int64 bit patterns (the kernels' dsac_sm64)."""
+    x = x + _i64(0x9E3779B97F4A7C15)
+    x = (x ^ _lsr(x, 30)) * _i64(0xBF58476D1CE4E5B9)
+    x = (x ^ _lsr(x, 27)) * _i64(0x94D049BB133111EB)
+    return x ^ _lsr(x, 31)
+
+
+@torch.no_grad()
+def norepl_index(n: torch.Tensor, t: torch.Tensor, j: torch.Tensor,
+                 ctr: torch.Tensor, return_walk: bool = False):
+    """Elementwise ``(P_key(j mod n) + rot_key) mod n`` for int64 tensors
+    of one shape: shard sizes ``n`` (>= 1), shard numbers ``t``, row
+    positions ``j`` and rng counters ``ctr``.  ``P_key`` is ``NR_ROUNDS``
+    alternating unbalanced XOR-Feistel rounds over ``max(NR_MIN_BITS,
+    ceil(log2 n))`` bits, cycle-walked into ``[0, n)``.  With
+    ``return_walk`` also returns how many times each element applied the
+    network."""
+    n, t, j, ctr = (v.contiguous()
+                    for v in torch.broadcast_tensors(n, t, j, ctr))
+    key = _sm64(ctr * 0x100000001 + _i64(1 << 63) + t)
+    rot = _lsr(_sm64(key), 32) % n
+    b = torch.full_like(n, NR_MIN_BITS)
+    for k in range(NR_MIN_BITS, 32):   # ceil(log2 n) = #{k : 2^k < n}
+        b += (n > (1 << k)).to(b.dtype)
+    bl = b >> 1
+    one = torch.ones_like(n)
+    ml = (one << bl) - 1
+    mh = (one << (b - bl)) - 1
+    x = j % n
+    walk = torch.zeros_like(n)
+    todo = torch.ones_like(n, dtype=torch.bool)
+    while bool(todo.any()):
+        lo, hi = x & ml, x >> bl
+        for r in range(NR_ROUNDS):
+            kr = key + ((r + 1) << 32)
+            if r % 2 == 0:
+                lo = lo ^ (_lsr(_sm64(kr + hi), 32) & ml)
+            else:
+                hi = hi ^ (_lsr(_sm64(kr + lo), 32) & mh)
+        x = torch.where(todo, (hi << bl) | lo, x)
+        walk += todo.to(walk.dtype)
+        todo = todo & (x >= n)
+    idx = (x + rot) % n
+    return (idx, walk) if return_walk else idx
+
+
+@torch.no_grad()
+def replay_sample_indices_norepl(sizes, B: int, T: int, ctr) -> torch.Tensor:
+    """In-shard indices of a stratified without-replacement draw: int64
+    ``[T * (B // T)]``, rows ``t * per .. (t + 1) * per - 1`` from shard
+    ``t``.  ``sizes`` holds the T shard sizes (tensor or sequence; an empty
+    shard yields index 0), ``ctr`` the rng counter (int or one-element
+    tensor).  Rows of one shard are distinct whenever its size is at least
+    ``per``; a smaller shard repeats its rows as evenly as possible."""
+    sizes = torch.as_tensor(sizes)
+    dev = sizes.device
+    per = int(B) // int(T)
+    n = sizes.reshape(-1)[:T].to(torch.int64).clamp(min=1)
+    if not torch.is_tensor(ctr):
+        ctr = torch.tensor(_i64(int(ctr)), dtype=torch.int64)
+    c = ctr.reshape(-1)[:1].to(device=dev, dtype=torch.int64)
+    t = torch.arange(T, device=dev, dtype=torch.int64)
+    j = torch.arange(per, device=dev, dtype=torch.int64)
+    return norepl_index(n[:, None], t[:, None], j[None, :],
+                        c[None, :]).reshape(-1)

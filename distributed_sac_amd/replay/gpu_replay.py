@@ -20,21 +20,28 @@ MT10_Distributed_MTSAC/src/replay_buffers.py:13-107 per-task deques):
   from each shard, shuffled concat) and ``len = min over shards`` —
   reference replay_buffers.py:37-41,67-100 semantics.
 
-Deviation from the reference, by design: minibatch indices are drawn with
-replacement (torch.randint) instead of ``random.sample``'s without-
-replacement draw — at batch 1280 from >=5000 entries the collision rate is
-<15% of samples and statistically immaterial for SAC, while avoiding a
-1e6-element randperm per update.
+Deviation from the reference, by default: minibatch indices are drawn with
+replacement (``floor(u * size)`` in ``k_replay_sample``, ``torch.randint``
+on the host path) where the reference's ``random.sample`` draws without —
+while a shard holds a few thousand entries, up to ~15% of a 1280 batch's
+rows collide (docs/PARITY.md).  ``sampling="without_replacement"`` (or
+``DSAC_SAMPLING=without_replacement``) restores the reference's
+semantics: each shard's rows of one batch are distinct, drawn by a keyed
+permutation evaluated per row (``k_replay_sample_norepl`` /
+``torch_ref.replay_sample_indices_norepl``) — inside the captured update,
+with no host round trip and no 1e6-element randperm.
 """
 
 from __future__ import annotations
 
+import os
 from typing import Dict, List, Optional
 
 import numpy as np
 import torch
 
 FIELDS = ("states", "actions", "rewards", "next_states", "dones")
+SAMPLING_MODES = ("replace", "without_replacement")
 
 
 class ReplayShard:
@@ -174,7 +181,17 @@ class ShardedReplay:
 
     def __init__(self, buffer_size: int, num_tasks: int, state_dim: int,
                  action_dim: int, device: torch.device | str = "cpu",
-                 seed: Optional[int] = None):
+                 seed: Optional[int] = None,
+                 sampling: Optional[str] = None):
+        # "replace" (default): independent uniform draws per row;
+        # "without_replacement": each shard's rows of a batch are distinct
+        # (the reference's random.sample), drawn by a keyed permutation
+        if sampling is None:
+            sampling = os.environ.get("DSAC_SAMPLING", "replace")
+        if sampling not in SAMPLING_MODES:
+            raise ValueError(f"sampling must be 'replace' or "
+                             f"'without_replacement', got {sampling!r}")
+        self.sampling = sampling
         self.num_tasks = num_tasks
         self.device = torch.device(device)
         per_task = int(buffer_size) // num_tasks  # reference replay_buffers.py:37-41
@@ -514,6 +531,48 @@ class ShardedReplay:
             fields["next_states"], fields["dones"])
 
     @torch.no_grad()
+    def sample_indices_norepl(self, batch_size: int) -> torch.Tensor:
+        """In-shard indices of one without-replacement draw (the torch
+        oracle): int64 ``[T * (batch_size // T)]``, shard-major.  Keyed by
+        the attached rng counter if there is one, otherwise by an int64
+        drawn from this replay's generator per call."""
+        from ..ops import torch_ref
+        ctr = self._rng_ctr
+        if ctr is None:
+            ctr = torch.randint(0, 1 << 62, (1,), device=self.device,
+                                generator=self.generator)
+        return torch_ref.replay_sample_indices_norepl(
+            self.sizes_dev, batch_size, self.num_tasks, ctr)
+
+    def _sample_norepl(self, batch_size: int,
+                       graph_safe: bool) -> Dict[str, torch.Tensor]:
+        T = self.num_tasks
+        fields = (self.f_states, self.f_actions, self.f_rewards,
+                  self.f_next_states, self.f_dones)
+        if graph_safe and self.device.type == "cuda" \
+                and batch_size % T == 0:
+            from ..ops import native, native_enabled
+            if native_enabled():
+                if self._rng_ctr is None:
+                    raise RuntimeError(
+                        "sampling='without_replacement' draws its graph-safe "
+                        "batches in k_replay_sample_norepl, which needs the "
+                        "engine's device rng counter: call attach_rng() "
+                        "(engine.capture does) and leave DSAC_KRNG at 1")
+                o = native().replay_sample_norepl(
+                    *fields, self.sizes_dev, batch_size, self._rng_ctr)
+                return dict(zip(FIELDS, o))
+        per = batch_size // T
+        cap = self.f_states.shape[1]
+        idx = self.sample_indices_norepl(batch_size)
+        idx += torch.arange(T, device=self.device).repeat_interleave(per) * cap
+        if not graph_safe and T > 1:   # the reference's shuffled concat
+            idx = idx[torch.randperm(per * T, device=self.device,
+                                     generator=self.generator)]
+        return {name: f.reshape(T * cap, -1).index_select(0, idx)
+                for name, f in zip(FIELDS, fields)}
+
+    @torch.no_grad()
     def sample(self, batch_size: int,
                graph_safe: bool = False) -> Dict[str, torch.Tensor]:
         """Stratified across shards, shuffled concat (reference
@@ -524,9 +583,17 @@ class ShardedReplay:
         permutation-invariant: all losses are batch means).
 
         Pending packed batches are flushed first, so the host-side sizes
-        the non-graph draw uses match what is in device memory."""
+        the non-graph draw uses match what is in device memory.
+
+        With ``sampling="without_replacement"`` each shard's rows are
+        distinct (while the shard holds at least ``batch_size //
+        num_tasks`` rows): graph_safe=True on a GPU draws in
+        ``k_replay_sample_norepl``, every other path with the same
+        algorithm in torch."""
         if self._pk_pending:
             self.flush_packed()
+        if self.sampling == "without_replacement":
+            return self._sample_norepl(batch_size, graph_safe)
         gen = None if graph_safe else self.generator
         if graph_safe and self.device.type == "cuda":
             from ..ops import has_native, native, native_enabled

@@ -44,7 +44,8 @@ class Learner:
                  ddp=None, seed: int = 0, heartbeat=None,
                  heartbeat_timeout: float = 60.0, rings=None,
                  precision: str = None, publish_interval_s: float = 0.02,
-                 graph_chunk: int = 4, ingest: Optional[str] = None):
+                 graph_chunk: int = 4, ingest: Optional[str] = None,
+                 sampling: Optional[str] = None):
         self.cfg = cfg
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -58,9 +59,19 @@ class Learner:
         if ddp is not None:
             self.engine.attach_ddp(ddp)
         num_tasks = cfg.num_tasks if cfg.variant in ("mtsac", "care") else 1
+        # replay draw: the argument, else a cfg that names replay_sampling,
+        # else the replay's own default (DSAC_SAMPLING, else "replace")
+        if sampling is None:
+            sampling = cfg.replay_sampling_choice
         self.replay = ShardedReplay(cfg.buffer_size, num_tasks,
                                     cfg.mtobs_dim, cfg.action_dim,
-                                    device=device, seed=seed)
+                                    device=device, seed=seed,
+                                    sampling=sampling)
+        if self.replay.sampling == "without_replacement" \
+                and getattr(self.engine, "_use_krng", False):
+            # the in-kernel draw is keyed by the engine's rng counter;
+            # capture() attaches it too, the eager GPU path needs it here
+            self.replay.attach_rng(self.engine._rng_ctr)
         self.snapshot = snapshot
         self.sample_queue = sample_queue
         self.rings = rings or []

@@ -51,7 +51,8 @@ class DistributedTrainer:
                  chunk_steps: int = 64, seed: int = 0, use_graph: bool = True,
                  ddp=None, transport: str = "auto", precision: str = None,
                  eval_every_episodes: int = 0,
-                 ingest: Optional[str] = None):
+                 ingest: Optional[str] = None,
+                 sampling: Optional[str] = None):
         self.cfg = cfg
         self.env_fn = env_fn or default_env_fn
         self.ctx = mp.get_context("spawn")
@@ -92,7 +93,8 @@ class DistributedTrainer:
                                save_dir=save_dir, save_period=save_period,
                                use_graph=use_graph, ddp=ddp, seed=seed,
                                heartbeat=self.heartbeat, rings=self.rings,
-                               precision=precision, ingest=ingest)
+                               precision=precision, ingest=ingest,
+                               sampling=sampling)
 
     def _spawn_player(self, pid: int, seed_bump: int = 0) -> "mp.Process":
         p = self.ctx.Process(

@@ -55,7 +55,8 @@ class Trainer:
         num_tasks = cfg.num_tasks if cfg.variant in ("mtsac", "care") else 1
         self.replay = ShardedReplay(cfg.buffer_size, num_tasks,
                                     cfg.mtobs_dim, cfg.action_dim,
-                                    device=device, seed=seed)
+                                    device=device, seed=seed,
+                                    sampling=cfg.replay_sampling_choice)
         env_fn = env_fn or default_env_fn
         envs, tasks = [], []
         for t in range(num_tasks):
