@@ -26,6 +26,7 @@ in the actor step) run under no_grad — numerically identical updates.
 
 from __future__ import annotations
 
+import os
 from typing import Dict, Optional
 
 import torch
@@ -35,6 +36,7 @@ from ..config import SACConfig
 from ..models.care import CAREActor, CARECritic
 from ..models.context_encoder import contextEncoder
 from ..ops import functional as Fops
+from ..ops.chain import ManualChain, mlp_bwd_arena, pack_chains
 from ..ops.flat import FlatParams, FusedAdam
 from .sac import SACEngine
 
@@ -273,8 +275,7 @@ class CAREEngine(SACEngine):
         dev = self.device
 
         def mlp_linears(seq):
-            import torch.nn as nn_
-            return [m for m in seq if isinstance(m, nn_.Linear)]
+            return [m for m in seq if isinstance(m, nn.Linear)]
 
         def build(critic, group, mirror):
             se = critic.state_encoder
@@ -293,16 +294,9 @@ class CAREEngine(SACEngine):
                     info[name] = None
                     continue
                 lins = mlp_linears(seq)
-                ws, bs, wsh = [], [], []
-                for l in lins:
-                    i = next(j for j, q in enumerate(group.params)
-                             if q is l.weight)
-                    off = group.offsets[i]
-                    wsh.append(mirror[off:off + l.weight.numel()]
-                               .view_as(l.weight))
-                    ws.append(l.weight)
-                    bs.append(l.bias)
-                info[name] = (ws, bs, wsh)
+                ws = [l.weight for l in lins]
+                info[name] = (ws, [l.bias for l in lins],
+                              self._mirror_views(group, mirror, ws))
             # fused narrow-chain eligibility: every layer <= 64 wide,
             # <= 6 layers (k_bf16_mlp_narrow constraints)
             def narrow_ok(widths, L):
@@ -324,40 +318,22 @@ class CAREEngine(SACEngine):
         self._refresh_mixT()
 
         # original-CARE trainable context encoder (round 2): bf16 mirror
-        # + W^T buffers so the manual path can run the context chain on
-        # the fused chain kernels (fwd + dx + grouped dwdb, third arena)
+        # so the manual path can run the context chain on the fused chain
+        # kernels (fwd + dx + grouped dwdb, third arena) — in both
+        # DSAC_CHAIN modes
         self._ctx_chain = None
         if self.context_group is not None:
-            import torch.nn as nn_
-            lins = [m for m in self.context_encoder.modules()
-                    if isinstance(m, nn_.Linear)]
+            lins = mlp_linears(self.context_encoder.modules())
             grp = self.context_group
-            mir = torch.empty(grp.numel, dtype=torch.bfloat16, device=dev)
-            ws16, wts, bss = [], [], []
-            for l in lins:
-                i = next(j for j, q in enumerate(grp.params)
-                         if q is l.weight)
-                off = grp.offsets[i]
-                ws16.append(mir[off:off + l.weight.numel()]
-                            .view_as(l.weight))
-                wts.append(torch.empty(l.weight.shape[1],
-                                       l.weight.shape[0],
-                                       dtype=torch.bfloat16, device=dev))
-                bss.append(l.bias)
-            mir.copy_(grp.flat_data)
-            self.context_encoder_optimizer.bf16_mirror = mir
-
-            def _fpx(w, dx):
-                K = w.shape[-1]
-                N = w.numel() // K
-                r, c = (K, N) if dx else (N, K)
-                return torch.empty(
-                    ((r + 15) // 16) * ((c + 31) // 32) * 512,
-                    dtype=torch.bfloat16, device=dev)
-            self._ctx_chain = {"mir": mir, "ws16": ws16, "wt": wts,
-                               "bs": bss, "lins": lins,
-                               "fp": [_fpx(w, False) for w in ws16],
-                               "dxp": [_fpx(w, True) for w in ws16]}
+            ws = [l.weight for l in lins]
+            bs = [l.bias for l in lins]
+            self._ctx_bf16 = torch.empty(grp.numel, dtype=torch.bfloat16,
+                                         device=dev)
+            self._ctx_bf16.copy_(grp.flat_data)
+            self.context_encoder_optimizer.bf16_mirror = self._ctx_bf16
+            self._ctx_chain = ManualChain(
+                self._mirror_views(grp, self._ctx_bf16, ws), bs, group=grp,
+                w_params=ws, b_params=bs, always_chain=True)
 
     @torch.no_grad()
     def _refresh_mixT(self, which: str = "all") -> None:
@@ -375,7 +351,7 @@ class CAREEngine(SACEngine):
         super().refresh_bf16(which)
         self._refresh_mixT(which)
         if which == "all" and getattr(self, "_ctx_chain", None) is not None:
-            self._ctx_chain["mir"].copy_(self.context_group.flat_data)
+            self._ctx_bf16.copy_(self.context_group.flat_data)
 
     def _se_fwd_fast(self, info, mtobss_2d, z_context):
         """stateEncoder.forward via bf16 kernels (value-identical to the
@@ -402,7 +378,7 @@ class CAREEngine(SACEngine):
         if getattr(self, "_bf16", False):
             if which == "target":
                 return Fops.twin_mlp_forward_bf16(x, *self._twin_target,
-                                                  self._twin_target_bf16)
+                                                  self._target_chain.ws16)
             if which == "frozen":
                 return Fops.twin_mlp_forward_bf16(x,
                                                   *self._twin_local_frozen,
@@ -421,12 +397,10 @@ class CAREEngine(SACEngine):
         under no_grad (see module doc); the actor head runs ONE batched
         pass over cat(next, states) like the SAC engine (the actor-side
         state encoder is no-grad in both halves)."""
-        import os as _os
         manual_ok = getattr(self, "_se_fast", False) and (
             self.use_modified_care
-            or (getattr(self, "_ctx_chain", None) is not None
-                and self._use_chain))
-        if manual_ok and _os.environ.get("DSAC_NO_MANUAL", "0") != "1":
+            or getattr(self, "_ctx_chain", None) is not None)
+        if manual_ok and os.environ.get("DSAC_NO_MANUAL", "0") != "1":
             return self._update_tensors_manual(batch)
         from ..ops import native
         states, actions = batch["states"], batch["actions"]
@@ -708,29 +682,12 @@ class CAREEngine(SACEngine):
         sd = states.shape[1] - T                 # raw state dim
         D = self._se_local["mixW"][-1].shape[2]
         info = self._se_local
-        nl_c = len(self._twin_local_bf16)
-        nl_a = len(self._actor_ws_bf16)
         orig = not self.use_modified_care
-        chain0 = self._use_chain
-        if chain0:
-            # ONE launch re-packs every pre-step weight set
-            ws_pack = (list(self._twin_local_bf16) * 2
-                       + list(self._twin_target_bf16)
-                       + list(self._actor_ws_bf16) * 2)
-            ps_pack = (list(self._twin_local_fp)
-                       + list(self._twin_local_dxp)
-                       + list(self._twin_target_fp)
-                       + list(self._actor_fp) + list(self._actor_dxp))
-            gs_pack = [2] * (3 * nl_c) + [1] * (2 * nl_a)
-            dx_pack = ([0] * nl_c + [1] * nl_c + [0] * nl_c
-                       + [0] * nl_a + [1] * nl_a)
-            if orig:
-                cc0 = self._ctx_chain
-                ws_pack += list(cc0["ws16"]) * 2
-                ps_pack += list(cc0["fp"]) + list(cc0["dxp"])
-                gs_pack += [1] * (2 * len(cc0["ws16"]))
-                dx_pack += [0] * len(cc0["ws16"]) + [1] * len(cc0["ws16"])
-            ext.pack_weights_frag(ws_pack, ps_pack, gs_pack, dx_pack)
+        # ONE launch re-packs every pre-step weight set
+        pack_chains(ext, [(self._critic_chain, True, True),
+                          (self._target_chain, True, False),
+                          (self._actor_chain, True, True)]
+                    + ([(self._ctx_chain, True, True)] if orig else []))
 
         if orig:
             # original CARE: TRAINABLE context encoder (embedding header +
@@ -738,13 +695,9 @@ class CAREEngine(SACEngine):
             # frozen embeddings; activations saved for the third-arena
             # backward below (reference MT1…/learner.py: context grads
             # come from the critic loss only)
-            cc = self._ctx_chain
             idx = states[:, -T:].argmax(dim=1)
             emb = torch.relu(self.context_encoder.embedding[0](idx))
-            z_context, acts_ctx = self._chain_fwd(
-                emb, None, cc["ws16"], cc["bs"], G=1, act_last=0,
-                out_f32=True,
-                wps=cc["fp"] if self._use_chain else None)
+            z_context, acts_ctx = self._ctx_chain.forward(emb)
         else:
             z_context = self.context_encoder(states)     # frozen embedding
             acts_ctx = None
@@ -760,15 +713,7 @@ class CAREEngine(SACEngine):
                                                 zc16, save=True, rep=2)
 
         # ---- batched actor head + squash ------------------------------
-        ws_f32, bs_f32 = self._actor_weights()
-        chain = self._use_chain
-        if chain:
-            out, acts_a = self._chain_fwd(enc_cat, None,
-                                          self._actor_ws_bf16, bs_f32,
-                                          G=1, wps=self._actor_fp)
-        else:
-            out, acts_a = self._mlp_fwd_manual(enc_cat, self._actor_ws_bf16,
-                                               bs_f32)
+        out, acts_a = self._actor_chain.forward(enc_cat)
         mu, lsr = out[:, :A], out[:, A:]
         krng = self._use_krng and not self._eps_queue
         if self._eps_queue:
@@ -789,71 +734,22 @@ class CAREEngine(SACEngine):
         enc_t, _ = self._se_fwd_manual(self._se_target,
                                        next_states[:, :sd].to(torch.bfloat16),
                                        zc16)
-        if chain:
-            yt, _ = self._chain_fwd(enc_t, na, self._twin_target_bf16,
-                                    self._twin_target[1], G=2,
-                                    save_acts=False,
-                                    wps=self._twin_target_fp)
-            q1_t, q2_t = yt[0], yt[1]
-        else:
-            xt = torch.cat([enc_t, na.to(torch.bfloat16)], dim=-1)
-            q1_t, q2_t, _ = self._twin_fwd_manual(xt,
-                                                  self._twin_target_bf16,
-                                                  self._twin_target[1])
+        (q1_t, q2_t), _ = self._target_chain.forward(enc_t, na,
+                                                     save_acts=False)
         y = ext.td_target_mt(rewards, dones, q1_t, q2_t, nlp, states,
                              la_det, T, self.gamma, self.reward_scale)
 
         # ---- critic loss + manual backward ----------------------------
-        if chain:
-            yq, acts_q = self._chain_fwd(enc_cat[B:], actions,
-                                         self._twin_local_bf16,
-                                         self._twin_local[1], G=2,
-                                         wps=self._twin_local_fp)
-            q1, q2 = yq[0], yq[1]
-            head_in_dim = acts_q[0].shape[-1]
-        else:
-            x = torch.cat([enc_cat[B:], actions.to(torch.bfloat16)], dim=-1)
-            q1, q2, acts_q = self._twin_fwd_manual(x, self._twin_local_bf16,
-                                                   self._twin_local[1])
-            head_in_dim = x.shape[1]
+        (q1, q2), acts_q = self._critic_chain.forward(enc_cat[B:], actions)
         closs = ext.critic_loss_fwd(q1, q2, y, states, la_det, T,
                                     int(use_w), self._loss_ws)[0]
         dy = ext.critic_loss_bwd2(q1, q2, y, states, la_det, closs, T,
                                   int(use_w))
-        wsg, bsg = self._twin_local
         fg_c = self.critic_group.flat_grad
         arena_c, S_c, ch_c = self._dw_arena("critic",
                                             self.critic_group.numel, B)
-        base_c = fg_c.data_ptr()
-        if chain:
-            empty_h = states.new_empty(0, dtype=torch.bfloat16)
-            youts_q = [acts_q[i + 1] for i in range(nl_c - 1)] + [empty_h]
-            aflags_q = [1] * (nl_c - 1) + [0]
-            outs = ext.mlp_chain_dx_bf16(dy, list(self._twin_local_wt),
-                                         youts_q, head_in_dim, aflags_q,
-                                         2, 1, 0,
-                                         list(self._twin_local_dxp))
-            dys_q, dx0f = outs[:-1], outs[-1]
-            dx0 = (dx0f[0] + dx0f[1]).to(torch.bfloat16)  # [B, se+A]
-            ext.dwdb_grouped_arena(
-                list(dys_q), [acts_q[i] for i in range(nl_c)], arena_c,
-                [(w.grad.data_ptr() - base_c) // 4 for w in wsg],
-                [(b.grad.data_ptr() - base_c) // 4 for b in bsg],
-                2, S_c, ch_c)
-        else:
-            for i in range(nl_c - 1, -1, -1):
-                act = 1 if i < nl_c - 1 else 0
-                yout = acts_q[i + 1] if i < nl_c - 1 else acts_q[i]
-                ext.linear_bwd_dwdb_arena(
-                    dy, acts_q[i], yout, act, 2, arena_c,
-                    (wsg[i].grad.data_ptr() - base_c) // 4,
-                    (bsg[i].grad.data_ptr() - base_c) // 4, S_c, ch_c, 0)
-                if i > 0:
-                    dy = ext.linear_bwd_dx_bf16(dy, self._twin_local_bf16[i],
-                                                yout, act, 2, 0)
-            dx0 = ext.linear_bwd_dx_bf16(dy, self._twin_local_bf16[0],
-                                         acts_q[1] if nl_c > 1 else acts_q[0],
-                                         1 if nl_c > 1 else 0, 2, 1)  # [B,se+A]
+        dx0 = self._critic_chain.backward(dy, acts_q, arena_c, S_c, ch_c,
+                                          dx0_lo=0)        # bf16 [B, se+A]
         # state-encoder backward (states half of the batched acts)
         zen = se_saved["z_encs"][:, B:].contiguous()     # f32 [k,B,D]
         dedup = se_saved.get("rep", 1) == 2
@@ -867,9 +763,15 @@ class CAREEngine(SACEngine):
         tws, tbs, twsh = info["trunk"]
         acts_m = ([se_saved["acts_m"][0][B:]]
                   + [a[:, B:].contiguous() for a in se_saved["acts_m"][1:]])
-        import os as _os
+        base = fg_c.data_ptr()
+
+        def offs(ps):
+            return [(p_.grad.data_ptr() - base) // 4 for p_ in ps]
+
+        def cur_half(acts):
+            return acts if dedup else [a[B:] for a in acts]
         use_fused_se_bwd = (
-            _os.environ.get("DSAC_NARROW_BWD", "1") == "1"
+            os.environ.get("DSAC_NARROW_BWD", "1") == "1"
             and info["mix_narrow"] and info["trunk_narrow"]
             and (mlpctx is None or info["ctx_narrow"]))
         if use_fused_se_bwd:
@@ -879,14 +781,8 @@ class CAREEngine(SACEngine):
             # test); whole-chain fused backward, one launch per chain,
             # partials per 64-row block.  DSAC_NARROW_BWD=0 restores the
             # per-layer path.
-            base = fg_c.data_ptr()
-
-            def offs(ps):
-                return [(p_.grad.data_ptr() - base) // 4 for p_ in ps]
             arena2, S2, _ = self._dw_arena("se@rowblocks",
                                            self.critic_group.numel, B)
-            def cur_half(acts):
-                return acts if dedup else [a[B:] for a in acts]
             # all three SE backward chains in ONE launch (round 2)
             dys_l, actss, wss_l = [], [], []
             w_os, b_os, Gl, trl = [], [], [], []
@@ -918,56 +814,30 @@ class CAREEngine(SACEngine):
             ext.reduce_arena(arena2, fg_c, S2, 0, se_n)
             ext.reduce_arena(arena_c, fg_c, S_c, se_n, -1)
         else:
-            def cur_half(acts):
-                return acts if dedup else [a[B:] for a in acts]
             if mlpctx is not None:
-                self._mlp_bwd_arena(ext, dx0[:, :zc_dim].contiguous(),
-                                    cur_half(se_saved["acts_c"]),
-                                    cwsh,
-                                    [w.grad for w in cws],
-                                    [b.grad for b in cbs],
-                                    fg_c, arena_c, S_c, ch_c)
-            self._mlp_bwd_arena(ext, dlogits,
-                                cur_half(se_saved["acts_t"]), twsh,
-                                [w.grad for w in tws],
-                                [b.grad for b in tbs],
-                                fg_c, arena_c, S_c, ch_c)
-            self._mlp_bwd_arena(ext, dzencs, acts_m, info["mixT"],
-                                [w.grad for w in info["mixW"]],
-                                [b.grad for b in info["mixB"]],
-                                fg_c, arena_c, S_c, ch_c,
-                                G=info["k"], transpose_w=1)
+                mlp_bwd_arena(ext, dx0[:, :zc_dim].contiguous(),
+                              cur_half(se_saved["acts_c"]), cwsh,
+                              offs(cws), offs(cbs), arena_c, S_c, ch_c)
+            mlp_bwd_arena(ext, dlogits, cur_half(se_saved["acts_t"]), twsh,
+                          offs(tws), offs(tbs), arena_c, S_c, ch_c)
+            mlp_bwd_arena(ext, dzencs, acts_m, info["mixT"],
+                          offs(info["mixW"]), offs(info["mixB"]),
+                          arena_c, S_c, ch_c, G=info["k"], transpose_w=1)
             ext.reduce_arena(arena_c, fg_c, S_c)
         if orig:
             # context-encoder backward: the only z_context gradient source
             # is the critic-loss concat half of dx0 (reference
             # retain_graph rule) — fused dx chain + grouped dwdb into the
             # context arena, Adam stepped at the end of the update
-            cc = self._ctx_chain
-            nlx = len(cc["ws16"])
-            dzc = dx0[:, :zc_dim].contiguous()
-            empty_h = states.new_empty(0, dtype=torch.bfloat16)
-            youts_x = [acts_ctx[i + 1] for i in range(nlx - 1)] + [empty_h]
-            dys_x = ext.mlp_chain_dx_bf16(
-                dzc, list(cc["wt"]), youts_x, acts_ctx[0].shape[-1],
-                [1] * (nlx - 1) + [0], 1, 1, -1, list(cc["dxp"]))
-            fgx = self.context_group.flat_grad
-            self.context_group.rebind_grads()
-            basex = fgx.data_ptr()
             arena_x, S_x, ch_x = self._dw_arena(
                 "ctx", self.context_group.numel, B)
-            ext.dwdb_grouped_arena(
-                list(dys_x), [acts_ctx[i] for i in range(nlx)], arena_x,
-                [(l.weight.grad.data_ptr() - basex) // 4
-                 for l in cc["lins"]],
-                [(l.bias.grad.data_ptr() - basex) // 4
-                 for l in cc["lins"]],
-                1, S_x, ch_x)
-            ext.reduce_arena(arena_x, fgx, S_x)
+            self._ctx_chain.backward(dx0[:, :zc_dim].contiguous(), acts_ctx,
+                                     arena_x, S_x, ch_x)
+            ext.reduce_arena(arena_x, self.context_group.flat_grad, S_x)
         self._dp_st = dict(
-            chain=chain, states=states, sd=sd, zc16=zc16, sa=sa, lp=lp,
+            states=states, sd=sd, zc16=zc16, sa=sa, lp=lp,
             ls_cat=ls_cat, B=B, eps=eps, tanh_u=tanh_u, lsr=lsr,
-            acts_a=acts_a, ws_f32=ws_f32, bs_f32=bs_f32, la_det=la_det,
+            acts_a=acts_a, la_det=la_det,
             T=T, use_w=use_w, closs=closs, orig=orig)
 
     @torch.no_grad()
@@ -975,15 +845,11 @@ class CAREEngine(SACEngine):
         from ..ops import native
         ext = native()
         st = self._dp_st
-        chain = st["chain"]
         states, sd, zc16 = st["states"], st["sd"], st["zc16"]
         sa, lp, ls_cat, B = st["sa"], st["lp"], st["ls_cat"], st["B"]
         eps, tanh_u, lsr = st["eps"], st["tanh_u"], st["lsr"]
-        acts_a, ws_f32, bs_f32 = st["acts_a"], st["ws_f32"], st["bs_f32"]
         la_det, T, use_w = st["la_det"], st["T"], st["use_w"]
         info = self._se_local
-        nl_c = len(self._twin_local_bf16)
-        nl_a = len(self._actor_ws_bf16)
         st["prolog"] = self._adam_prolog_all()
         # adam kernel refreshes the flat bf16 mirror
         self.critic_optimizer.step(pre_prologed=st["prolog"])
@@ -992,21 +858,9 @@ class CAREEngine(SACEngine):
         # ---- actor/alpha loss + manual backward -----------------------
         enc_c, _ = self._se_fwd_manual(info, states[:, :sd].to(torch.bfloat16),
                                        zc16)               # post-step SE
-        if chain:
-            # re-pack the POST-Adam critic (fwd + dx) in one launch
-            ext.pack_weights_frag(
-                list(self._twin_local_bf16) * 2,
-                list(self._twin_local_fp) + list(self._twin_local_dxp),
-                [2] * (2 * nl_c), [0] * nl_c + [1] * nl_c)
-            ya, acts_f = self._chain_fwd(enc_c, sa, self._twin_local_bf16,
-                                         self._twin_local[1], G=2,
-                                         wps=self._twin_local_fp)
-            aq1, aq2 = ya[0], ya[1]
-        else:
-            xa = torch.cat([enc_c, sa.to(torch.bfloat16)], dim=-1)
-            aq1, aq2, acts_f = self._twin_fwd_manual(xa,
-                                                     self._twin_local_bf16,
-                                                     self._twin_local[1])
+        # re-pack the POST-Adam critic (fwd + dx) in one launch
+        pack_chains(ext, [(self._critic_chain, True, True)])
+        (aq1, aq2), acts_f = self._critic_chain.forward(enc_c, sa)
         # fwd kernel zeroes the alpha flat grad in passing (bwd atomics
         # target) — no separate fill launch
         al = ext.actor_alpha_loss_fwd(aq1, aq2, lp, ls_cat[B:], states,
@@ -1016,61 +870,16 @@ class CAREEngine(SACEngine):
         daq, dlp = ext.actor_alpha_loss_bwd2(
             aq1, aq2, lp, states, la_det, al, self.alpha_group.flat_grad,
             T, int(use_w), self.H_bar_f, self._dla_ws)
-        if chain:
-            empty_h = states.new_empty(0, dtype=torch.bfloat16)
-            youts_f = [acts_f[i + 1] for i in range(nl_c - 1)] + [empty_h]
-            outs = ext.mlp_chain_dx_bf16(
-                daq, list(self._twin_local_wt), youts_f,
-                acts_f[0].shape[-1], [1] * (nl_c - 1) + [0], 2, 0,
-                enc_c.shape[1], list(self._twin_local_dxp))
-            dx0a = outs[-1]
-            dsa = dx0a              # twin heads summed inside squash bwd2
-        else:
-            dy = daq
-            for i in range(nl_c - 1, 0, -1):
-                act = 1 if i < nl_c - 1 else 0
-                yout = acts_f[i + 1] if i < nl_c - 1 else acts_f[i]
-                dy = ext.linear_bwd_dx_bf16(dy, self._twin_local_bf16[i],
-                                            yout, act, 2, 0)
-            dxa = ext.linear_bwd_dx_bf16(dy, self._twin_local_bf16[0],
-                                         acts_f[1] if nl_c > 1 else acts_f[0],
-                                         1 if nl_c > 1 else 0, 2, 1)
-            dsa = dxa[:, enc_c.shape[1]:].float()
+        # dQ/d(action) only; twin heads summed inside squash bwd2
+        dsa = self._critic_chain.input_grad(daq, acts_f, enc_c.shape[1])
         dhead = ext.squashed_gaussian_bwd2(
             dsa, dlp, lsr[B:], ls_cat[B:], eps[B:], tanh_u[B:],
             float(self.actor.k))
-        dy = dhead
         fg_a = self.actor_group.flat_grad
         arena_a, S_a, ch_a = self._dw_arena("actor",
                                             self.actor_group.numel, B)
-        base_a = fg_a.data_ptr()
-        if chain:
-            empty_h = states.new_empty(0, dtype=torch.bfloat16)
-            youts_a = [acts_a[i + 1][B:] for i in range(nl_a - 1)] \
-                + [empty_h]
-            dys_a = ext.mlp_chain_dx_bf16(
-                dhead, list(self._actor_wt), youts_a,
-                acts_a[0].shape[-1], [1] * (nl_a - 1) + [0], 1, 1, -1,
-                list(self._actor_dxp))
-            ext.dwdb_grouped_arena(
-                list(dys_a), [acts_a[i][B:] for i in range(nl_a)],
-                arena_a,
-                [(w.grad.data_ptr() - base_a) // 4 for w in ws_f32],
-                [(b.grad.data_ptr() - base_a) // 4 for b in bs_f32],
-                1, S_a, ch_a)
-        else:
-            for i in range(nl_a - 1, -1, -1):
-                act = 1 if i < nl_a - 1 else 0
-                yout = (acts_a[i + 1][B:] if i < nl_a - 1
-                        else acts_a[i][B:])
-                ext.linear_bwd_dwdb_arena(
-                    dy, acts_a[i][B:], yout, act, 1, arena_a,
-                    (ws_f32[i].grad.data_ptr() - base_a) // 4,
-                    (bs_f32[i].grad.data_ptr() - base_a) // 4, S_a, ch_a,
-                    0)
-                if i > 0:
-                    dy = ext.linear_bwd_dx_bf16(dy, self._actor_ws_bf16[i],
-                                                yout, act, 1, 1)
+        self._actor_chain.backward(dhead, st["acts_a"], arena_a, S_a, ch_a,
+                                   rows=slice(B, None))
         ext.reduce_arena(arena_a, fg_a, S_a)
         st["al"] = al
 

@@ -23,6 +23,7 @@ MI355X-first mechanics under the reference math:
 
 from __future__ import annotations
 
+import os
 from typing import Dict, Optional
 
 import torch
@@ -31,6 +32,7 @@ import torch.nn as nn
 from ..config import SACConfig
 from ..models import Actor, Critic, LLActor, LLCritic
 from ..ops import functional as Fops
+from ..ops.chain import ManualChain, pack_chains
 from ..ops.flat import FlatParams, FusedAdam, flat_polyak_
 
 
@@ -39,9 +41,8 @@ class SACEngine:
 
     def __init__(self, cfg: SACConfig, device: torch.device | str = "cpu",
                  precision: Optional[str] = None):
-        import os as _os
         self.precision = (precision or
-                          _os.environ.get("DSAC_PRECISION", "fp32"))
+                          os.environ.get("DSAC_PRECISION", "fp32"))
         self.cfg = cfg
         self.variant = cfg.variant
         self.device = torch.device(device)
@@ -117,9 +118,8 @@ class SACEngine:
             l1 = [c1_or_critic.first_layer] + list(c1_or_critic.layer_module)
             l2 = [c2.first_layer] + list(c2.layer_module)
         else:  # MT style: one module with Q_function_1/2 Sequentials
-            import torch.nn as nn_
-            l1 = [m for m in c1_or_critic.Q_function_1 if isinstance(m, nn_.Linear)]
-            l2 = [m for m in c1_or_critic.Q_function_2 if isinstance(m, nn_.Linear)]
+            l1 = [m for m in c1_or_critic.Q_function_1 if isinstance(m, nn.Linear)]
+            l2 = [m for m in c1_or_critic.Q_function_2 if isinstance(m, nn.Linear)]
         return list(zip(l1, l2))
 
     def _critic_layer_pairs(self, target: bool = False):
@@ -240,55 +240,36 @@ class SACEngine:
         self._twin_local_bf16 = self._stack_views(self.critic_group,
                                                   self._critic_bf16,
                                                   self._critic_layer_pairs())
-        self._twin_target_bf16 = self._stack_views(
-            self.target_group, self._target_bf16,
-            self._critic_layer_pairs(target=True))
         self.critic_optimizer.bf16_mirror = self._critic_bf16
         self.actor_optimizer.bf16_mirror = self._actor_bf16
-        ws, _ = self._actor_weights()
-        self._actor_ws_bf16 = []
-        for w in ws:
-            i = next(j for j, q in enumerate(self.actor_group.params)
-                     if q is w)
-            off = self.actor_group.offsets[i]
-            self._actor_ws_bf16.append(
-                self._actor_bf16[off:off + w.numel()].view_as(w))
-        # TRANSPOSED weight mirrors (shape carriers for the dx-chain
-        # binding; the VALUES now come from the fragment-packed mirrors
-        # below, so these are never refreshed on the packed path)
-        self._twin_local_wt = [
-            torch.empty(w.shape[0], w.shape[2], w.shape[1],
-                        dtype=torch.bfloat16, device=dev)
-            for w in self._twin_local_bf16]
-        self._actor_wt = [
-            torch.empty(w.shape[1], w.shape[0], dtype=torch.bfloat16,
-                        device=dev) for w in self._actor_ws_bf16]
-
-        # FRAGMENT-PACKED weight mirrors (k_bf16_pack_frag): the chain
-        # kernels' B-operand loads become base + lane*16 unit-stride
-        # (one contiguous 1 KiB line per wave) instead of 16 scattered
-        # cache lines — re-packed per update (pre-step set at seg1,
-        # post-critic-Adam set in seg2)
-        def _fp(w, G):
-            K = w.shape[-1]
-            N = w.numel() // (G * K)
-            return torch.empty(
-                G * ((N + 15) // 16) * ((K + 31) // 32) * 512,
-                dtype=torch.bfloat16, device=dev)
-
-        def _dxp(w, G):
-            K = w.shape[-1]
-            N = w.numel() // (G * K)
-            return torch.empty(
-                G * ((K + 15) // 16) * ((N + 31) // 32) * 512,
-                dtype=torch.bfloat16, device=dev)
-
-        self._twin_local_fp = [_fp(w, 2) for w in self._twin_local_bf16]
-        self._twin_target_fp = [_fp(w, 2) for w in self._twin_target_bf16]
-        self._actor_fp = [_fp(w, 1) for w in self._actor_ws_bf16]
-        self._twin_local_dxp = [_dxp(w, 2) for w in self._twin_local_bf16]
-        self._actor_dxp = [_dxp(w, 1) for w in self._actor_ws_bf16]
+        ws, bs = self._actor_weights()
+        self._actor_ws_bf16 = self._mirror_views(self.actor_group,
+                                                 self._actor_bf16, ws)
+        # the manual update's chains; their fragment-packed weights are
+        # re-packed per update (pre-step sets in seg1, the post-Adam
+        # critic in seg2)
+        pairs = self._critic_layer_pairs()
+        self._critic_chain = ManualChain(
+            self._twin_local_bf16, self._twin_local[1], G=2,
+            group=self.critic_group,
+            w_params=[l1.weight for l1, _ in pairs],
+            b_params=[l1.bias for l1, _ in pairs])
+        self._target_chain = ManualChain(
+            self._stack_views(self.target_group, self._target_bf16,
+                              self._critic_layer_pairs(target=True)),
+            self._twin_target[1], G=2, dx=False)
+        self._actor_chain = ManualChain(
+            self._actor_ws_bf16, bs, group=self.actor_group,
+            w_params=ws, b_params=bs)
         self.refresh_bf16()
+
+    @staticmethod
+    def _mirror_views(group, mirror, ws):
+        """bf16 mirror views shaped like the fp32 weights ``ws``."""
+        offs = [group.offsets[next(j for j, q in enumerate(group.params)
+                                   if q is w)] for w in ws]
+        return [mirror[off:off + w.numel()].view_as(w)
+                for w, off in zip(ws, offs)]
 
     @staticmethod
     def _stack_views(group, mirror, pairs):
@@ -366,7 +347,7 @@ class SACEngine:
             x = torch.cat([states, actions], dim=-1)
             if getattr(self, "_bf16", False):
                 return Fops.twin_mlp_forward_bf16(x, *self._twin_target,
-                                                  self._twin_target_bf16)
+                                                  self._target_chain.ws16)
             return Fops.twin_mlp_forward(x, *self._twin_target)
         if self.variant in ("sac", "vsac"):
             return (self.target_critic_1(states, actions),
@@ -482,42 +463,9 @@ class SACEngine:
             bs = [m.bias for m in self.actor.layer_intermediate] \
                 + [self.actor.mu_log_std_layer.bias]
             return ws, bs
-        import torch.nn as nn_
         lins = [m for m in self.actor.mu_log_std_layer
-                if isinstance(m, nn_.Linear)]
+                if isinstance(m, nn.Linear)]
         return [m.weight for m in lins], [m.bias for m in lins]
-
-    @torch.no_grad()
-    def _mlp_fwd_manual(self, x_f32, ws_bf16, bs_f32):
-        from ..ops import native
-        ext = native()
-        xh = x_f32.to(torch.bfloat16)
-        acts = [xh]
-        h = xh
-        n = len(ws_bf16)
-        for i in range(n):
-            last = i == n - 1
-            h = ext.linear_act_fwd_bf16(h, ws_bf16[i], bs_f32[i].contiguous(),
-                                        0 if last else 1, 1,
-                                        1 if last else 0)
-            acts.append(h)
-        return h, acts
-
-    @torch.no_grad()
-    def _twin_fwd_manual(self, x_f32, ws_bf16, bs_f32):
-        from ..ops import native
-        ext = native()
-        xh = x_f32.to(torch.bfloat16)
-        acts = [xh]
-        h = xh
-        n = len(ws_bf16)
-        for i in range(n):
-            last = i == n - 1
-            h = ext.linear_act_fwd_bf16(h, ws_bf16[i], bs_f32[i].contiguous(),
-                                        0 if last else 1, 2,
-                                        1 if last else 0)
-            acts.append(h)
-        return h[0], h[1], acts
 
     def _dw_arena(self, name: str, numel: int, B: int):
         """[S, group_numel] fp32 split-K arena for one backward phase:
@@ -540,24 +488,6 @@ class SACEngine:
             store[key] = (torch.empty(S, numel, device=self.device),
                           S, chunk)
         return store[key]
-
-    @staticmethod
-    def _mlp_bwd_arena(ext, dy, acts, wsh, ws_grad, bs_grad, flat_grad,
-                       arena, S, chunk, G=1, transpose_w=0):
-        """Backward an act-fwd chain; dW/db partials go to the phase arena
-        at the layer's flat-grad offsets (fold happens once per phase)."""
-        n = len(wsh)
-        base = flat_grad.data_ptr()
-        for i in range(n - 1, -1, -1):
-            act = 1 if i < n - 1 else 0
-            yout = acts[i + 1] if i < n - 1 else acts[i]
-            ext.linear_bwd_dwdb_arena(
-                dy, acts[i], yout, act, G, arena,
-                (ws_grad[i].data_ptr() - base) // 4,
-                (bs_grad[i].data_ptr() - base) // 4, S, chunk, transpose_w)
-            if i > 0:
-                dy = ext.linear_bwd_dx_bf16(dy, wsh[i], yout, act, G, 0)
-        return dy
 
     @torch.no_grad()
     def _update_tensors_manual(self, batch):
@@ -585,24 +515,14 @@ class SACEngine:
         return self._manual_seg3()
 
     @property
-    def _use_chain(self) -> bool:
-        """Fused MLP-chain forward kernels (one launch per chain,
-        in-kernel f32 concat+cast input — kills the per-layer launch
-        latency plus the cat/cast launches; round-2).  DSAC_CHAIN=0
-        restores the per-layer path."""
-        import os as _os
-        return _os.environ.get("DSAC_CHAIN", "1") == "1"
-
-    @property
     def _use_krng(self) -> bool:
         """Counter-based device RNG inside the squash / replay-sample
         kernels (round 2): replaces the torch rand+randn launches and the
         hipGraph RNG-offset bookkeeping kernels.  DSAC_KRNG=0 restores
         torch's philox draws."""
-        import os as _os
         return (getattr(self, "_bf16", False)
                 and getattr(self, "_rng_ctr", None) is not None
-                and _os.environ.get("DSAC_KRNG", "1") == "1")
+                and os.environ.get("DSAC_KRNG", "1") == "1")
 
     @property
     def _fuse_tail(self) -> bool:
@@ -612,8 +532,7 @@ class SACEngine:
         with DP the all-reduce sits between fold and Adam), and Polyak
         inside the actor+alpha Adam launch.  Bit-identical results;
         DSAC_FUSE_TAIL=0 restores the separate launches."""
-        import os as _os
-        return _os.environ.get("DSAC_FUSE_TAIL", "1") == "1"
+        return os.environ.get("DSAC_FUSE_TAIL", "1") == "1"
 
     def _adam_prolog_all(self) -> bool:
         """ONE launch advances every optimizer's Adam state (+ RNG bump)
@@ -637,18 +556,6 @@ class SACEngine:
         return True
 
     @torch.no_grad()
-    def _chain_fwd(self, x1, x2, ws_bf16, bs_f32, G, act_last=0,
-                   out_f32=True, rowcat=False, save_acts=True, wps=None):
-        from ..ops import native
-        out = native().mlp_chain_fwd_bf16(
-            x1, x2 if x2 is not None else x1.new_empty(0),
-            list(ws_bf16), [b.contiguous() for b in bs_f32],
-            int(act_last), int(G), 1 if out_f32 else 0, 0,
-            1 if rowcat else 0, 1 if save_acts else 0,
-            list(wps) if wps is not None else [])
-        return out[0], [out[1]] + list(out[2:])
-
-    @torch.no_grad()
     def _manual_seg1(self, batch):
         """Segment 1: batched actor forward + squash, TD target, critic
         loss forward + backward.  Ends with the critic flat gradient ready
@@ -665,34 +572,15 @@ class SACEngine:
         B = states.shape[0]
         A = self.cfg.action_dim
         la_det = self.log_alpha.detach()
-        chain = self._use_chain
-        if chain:
-            # ONE launch re-packs every pre-step weight set into the
-            # fragment layout (critic fwd+dx, target fwd, actor fwd+dx)
-            nl_c0 = len(self._twin_local_bf16)
-            nl_a0 = len(self._actor_ws_bf16)
-            ext.pack_weights_frag(
-                list(self._twin_local_bf16) * 2
-                + list(self._twin_target_bf16)
-                + list(self._actor_ws_bf16) * 2,
-                list(self._twin_local_fp) + list(self._twin_local_dxp)
-                + list(self._twin_target_fp)
-                + list(self._actor_fp) + list(self._actor_dxp),
-                [2] * (3 * nl_c0) + [1] * (2 * nl_a0),
-                [0] * nl_c0 + [1] * nl_c0 + [0] * nl_c0
-                + [0] * nl_a0 + [1] * nl_a0)
+        # ONE launch re-packs every pre-step weight set into the
+        # fragment layout (critic fwd+dx, target fwd, actor fwd+dx)
+        pack_chains(ext, [(self._critic_chain, True, True),
+                          (self._target_chain, True, False),
+                          (self._actor_chain, True, True)])
 
         # ---- batched actor forward + squash --------------------------
-        ws_f32, bs_f32 = self._actor_weights()
-        if chain:
-            out, acts_a = self._chain_fwd(next_states, states,
-                                          self._actor_ws_bf16, bs_f32,
-                                          G=1, rowcat=True,
-                                          wps=self._actor_fp)
-        else:
-            x_cat = torch.cat([next_states, states], dim=0)
-            out, acts_a = self._mlp_fwd_manual(x_cat, self._actor_ws_bf16,
-                                               bs_f32)
+        out, acts_a = self._actor_chain.forward(next_states, states,
+                                                rowcat=True)
         mu, lsr = out[:, :A], out[:, A:]
         krng = self._use_krng and not self._eps_queue
         if self._eps_queue:
@@ -709,17 +597,8 @@ class SACEngine:
         na, nlp = a_cat[:B], lp_cat[:B]
 
         # ---- TD target ------------------------------------------------
-        if chain:
-            yt, _ = self._chain_fwd(next_states, na,
-                                    self._twin_target_bf16,
-                                    self._twin_target[1], G=2,
-                                    save_acts=False,
-                                    wps=self._twin_target_fp)
-            q1_t, q2_t = yt[0], yt[1]
-        else:
-            xt = torch.cat([next_states, na], dim=-1)
-            q1_t, q2_t, _ = self._twin_fwd_manual(
-                xt, self._twin_target_bf16, self._twin_target[1])
+        (q1_t, q2_t), _ = self._target_chain.forward(next_states, na,
+                                                     save_acts=False)
         fuse = self._fuse_tail
         # one launch for TD target + loss fwd + dq (its grid covers the
         # batch in <= 32 blocks); a larger batch keeps the three launches
@@ -729,16 +608,7 @@ class SACEngine:
                                  la_det, T, self.gamma, self.reward_scale)
 
         # ---- critic loss + manual backward ---------------------------
-        if chain:
-            yq, acts_c = self._chain_fwd(states, actions,
-                                         self._twin_local_bf16,
-                                         self._twin_local[1], G=2,
-                                         wps=self._twin_local_fp)
-            q1, q2 = yq[0], yq[1]
-        else:
-            x = torch.cat([states, actions], dim=-1)
-            q1, q2, acts_c = self._twin_fwd_manual(
-                x, self._twin_local_bf16, self._twin_local[1])
+        (q1, q2), acts_c = self._critic_chain.forward(states, actions)
         if fuse_loss:
             closs, dy = ext.critic_td_loss(
                 rewards, dones, q1_t, q2_t, nlp, q1, q2, states, la_det, T,
@@ -748,29 +618,10 @@ class SACEngine:
                                         int(use_w), self._loss_ws)[0]
             dy = ext.critic_loss_bwd2(q1, q2, y, states, la_det, closs, T,
                                       int(use_w))
-        wsg = [w.grad for w in self._twin_local[0]]
-        bsg = [b.grad for b in self._twin_local[1]]
         fg_c = self.critic_group.flat_grad
         arena_c, S_c, ch_c = self._dw_arena("critic",
                                             self.critic_group.numel, B)
-        if chain:
-            nl_c = len(self._twin_local_bf16)
-            empty_h = states.new_empty(0, dtype=torch.bfloat16)
-            youts = [acts_c[i + 1] for i in range(nl_c - 1)] + [empty_h]
-            aflags = [1] * (nl_c - 1) + [0]
-            dys = ext.mlp_chain_dx_bf16(dy, list(self._twin_local_wt),
-                                        youts, acts_c[0].shape[-1],
-                                        aflags, 2, 1, -1,
-                                        list(self._twin_local_dxp))
-            base_c = fg_c.data_ptr()
-            ext.dwdb_grouped_arena(
-                list(dys), [acts_c[i] for i in range(nl_c)], arena_c,
-                [(w.data_ptr() - base_c) // 4 for w in wsg],
-                [(b.data_ptr() - base_c) // 4 for b in bsg],
-                2, S_c, ch_c)
-        else:
-            self._mlp_bwd_arena(ext, dy, acts_c, self._twin_local_bf16,
-                                wsg, bsg, fg_c, arena_c, S_c, ch_c, G=2)
+        self._critic_chain.backward(dy, acts_c, arena_c, S_c, ch_c)
         # single-GPU: the critic Adam kernel folds the arena itself; with
         # DP the all-reduce needs the folded gradient first
         fold_c = fuse and self.ddp is None
@@ -780,8 +631,7 @@ class SACEngine:
             "fuse": fuse, "arena_c": (arena_c, S_c) if fold_c else None,
             "states": states, "sa": a_cat[B:], "lp": lp_cat[B:],
             "lsr": lsr, "ls_cat": ls_cat, "eps": eps, "tanh_u": tanh_u,
-            "acts_a": acts_a, "ws_f32": ws_f32, "bs_f32": bs_f32,
-            "la_det": la_det, "closs": closs, "B": B,
+            "acts_a": acts_a, "la_det": la_det, "closs": closs, "B": B,
         }
 
     @torch.no_grad()
@@ -804,24 +654,10 @@ class SACEngine:
         use_w = self.use_weighted_loss
         la_det = st["la_det"]
         ls = st["ls_cat"][B:]
-        nl_a = len(self._actor_ws_bf16)
-        nl_c = len(self._twin_local_bf16)
-        acts_a = st["acts_a"]
 
-        if self._use_chain:
-            # re-pack the POST-Adam critic (fwd + dx) in one launch
-            ext.pack_weights_frag(
-                list(self._twin_local_bf16) * 2,
-                list(self._twin_local_fp) + list(self._twin_local_dxp),
-                [2] * (2 * nl_c), [0] * nl_c + [1] * nl_c)
-            ya, acts_f = self._chain_fwd(states, sa, self._twin_local_bf16,
-                                         self._twin_local[1], G=2,
-                                         wps=self._twin_local_fp)
-            aq1, aq2 = ya[0], ya[1]
-        else:
-            xa = torch.cat([states, sa], dim=-1)
-            aq1, aq2, acts_f = self._twin_fwd_manual(
-                xa, self._twin_local_bf16, self._twin_local[1])
+        # re-pack the POST-Adam critic (fwd + dx) in one launch
+        pack_chains(ext, [(self._critic_chain, True, True)])
+        (aq1, aq2), acts_f = self._critic_chain.forward(states, sa)
         # the fwd kernel zeroes the alpha flat grad in passing (the bwd's
         # atomics target) — no separate fill launch
         fuse = st["fuse"]
@@ -844,63 +680,17 @@ class SACEngine:
                 aq1, aq2, lp, states, la_det, al,
                 self.alpha_group.flat_grad, T, int(use_w), self.H_bar_f,
                 self._dla_ws)
-        if self._use_chain:
-            empty_h = states.new_empty(0, dtype=torch.bfloat16)
-            youts_f = [acts_f[i + 1] for i in range(nl_c - 1)] + [empty_h]
-            outs = ext.mlp_chain_dx_bf16(
-                daq, list(self._twin_local_wt), youts_f,
-                acts_f[0].shape[-1], [1] * (nl_c - 1) + [0], 2, 0,
-                states.shape[1], list(self._twin_local_dxp))
-            dx0 = outs[-1]          # [2, B, A] fp32 (action columns only)
-            dsa = dx0               # twin heads summed inside squash bwd2
-        else:
-            dy = daq
-            for i in range(nl_c - 1, 0, -1):
-                act = 1 if i < nl_c - 1 else 0
-                yout = acts_f[i + 1] if i < nl_c - 1 else acts_f[i]
-                dy = ext.linear_bwd_dx_bf16(dy, self._twin_local_bf16[i],
-                                            yout, act, 2, 0)
-            dxa = ext.linear_bwd_dx_bf16(
-                dy, self._twin_local_bf16[0],
-                acts_f[1] if nl_c > 1 else acts_f[0],
-                1 if nl_c > 1 else 0, 2, 1)
-            dsa = dxa[:, states.shape[1]:].float()
+        # dQ/d(action) only ([2, B, A] fp32 on the chain kernels); the twin
+        # heads are summed inside squash bwd2
+        dsa = self._critic_chain.input_grad(daq, acts_f, states.shape[1])
         dhead = ext.squashed_gaussian_bwd2(
             dsa, dlp, st["lsr"][B:], st["ls_cat"][B:], st["eps"][B:],
             st["tanh_u"][B:], float(self.actor.k))
-        wag = [w.grad for w in st["ws_f32"]]
-        bag = [b.grad for b in st["bs_f32"]]
         fg_a = self.actor_group.flat_grad
         arena_a, S_a, ch_a = self._dw_arena("actor",
                                             self.actor_group.numel, B)
-        base_a = fg_a.data_ptr()
-        if self._use_chain:
-            empty_h = states.new_empty(0, dtype=torch.bfloat16)
-            youts_a = [acts_a[i + 1][B:] for i in range(nl_a - 1)] \
-                + [empty_h]
-            dys_a = ext.mlp_chain_dx_bf16(
-                dhead, list(self._actor_wt), youts_a,
-                acts_a[0].shape[-1], [1] * (nl_a - 1) + [0], 1, 1, -1,
-                list(self._actor_dxp))
-            ext.dwdb_grouped_arena(
-                list(dys_a), [acts_a[i][B:] for i in range(nl_a)],
-                arena_a,
-                [(w.data_ptr() - base_a) // 4 for w in wag],
-                [(b.data_ptr() - base_a) // 4 for b in bag],
-                1, S_a, ch_a)
-        else:
-            dy = dhead
-            for i in range(nl_a - 1, -1, -1):
-                act = 1 if i < nl_a - 1 else 0
-                yout = (acts_a[i + 1][B:] if i < nl_a - 1
-                        else acts_a[i][B:])
-                ext.linear_bwd_dwdb_arena(
-                    dy, acts_a[i][B:], yout, act, 1, arena_a,
-                    (wag[i].data_ptr() - base_a) // 4,
-                    (bag[i].data_ptr() - base_a) // 4, S_a, ch_a, 0)
-                if i > 0:
-                    dy = ext.linear_bwd_dx_bf16(dy, self._actor_ws_bf16[i],
-                                                yout, act, 1, 1)
+        self._actor_chain.backward(dhead, st["acts_a"], arena_a, S_a, ch_a,
+                                   rows=slice(B, None))
         fold_a = fuse and self.ddp is None
         if not fold_a:
             ext.reduce_arena(arena_a, fg_a, S_a)
@@ -960,9 +750,8 @@ class SACEngine:
         B = states.shape[0]
         A = self.cfg.action_dim
 
-        import os as _os
         if getattr(self, "_bf16", False) \
-                and _os.environ.get("DSAC_NO_MANUAL", "0") != "1":
+                and os.environ.get("DSAC_NO_MANUAL", "0") != "1":
             return self._update_tensors_manual(batch)
         self.zero_grad()
 
