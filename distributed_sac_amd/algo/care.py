@@ -36,7 +36,8 @@ from ..config import SACConfig
 from ..models.care import CAREActor, CARECritic
 from ..models.context_encoder import contextEncoder
 from ..ops import functional as Fops
-from ..ops.chain import ManualChain, mlp_bwd_arena, pack_chains
+from ..ops.chain import (ManualChain, forward_pair, mlp_bwd_arena,
+                         pack_chains)
 from ..ops.flat import FlatParams, FusedAdam
 from .sac import SACEngine
 
@@ -734,13 +735,14 @@ class CAREEngine(SACEngine):
         enc_t, _ = self._se_fwd_manual(self._se_target,
                                        next_states[:, :sd].to(torch.bfloat16),
                                        zc16)
-        (q1_t, q2_t), _ = self._target_chain.forward(enc_t, na,
-                                                     save_acts=False)
+        # target heads + critic heads: independent chains, ONE launch
+        ((q1_t, q2_t), _), ((q1, q2), acts_q) = forward_pair(
+            (self._target_chain, (enc_t, na), {"save_acts": False}),
+            (self._critic_chain, (enc_cat[B:], actions), {}))
         y = ext.td_target_mt(rewards, dones, q1_t, q2_t, nlp, states,
                              la_det, T, self.gamma, self.reward_scale)
 
         # ---- critic loss + manual backward ----------------------------
-        (q1, q2), acts_q = self._critic_chain.forward(enc_cat[B:], actions)
         closs = ext.critic_loss_fwd(q1, q2, y, states, la_det, T,
                                     int(use_w), self._loss_ws)[0]
         dy = ext.critic_loss_bwd2(q1, q2, y, states, la_det, closs, T,

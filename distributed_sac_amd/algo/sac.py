@@ -32,7 +32,7 @@ import torch.nn as nn
 from ..config import SACConfig
 from ..models import Actor, Critic, LLActor, LLCritic
 from ..ops import functional as Fops
-from ..ops.chain import ManualChain, pack_chains
+from ..ops.chain import ManualChain, forward_pair, pack_chains
 from ..ops.flat import FlatParams, FusedAdam, flat_polyak_
 
 
@@ -596,9 +596,11 @@ class SACEngine:
             self._rng_ctr if krng else None)
         na, nlp = a_cat[:B], lp_cat[:B]
 
-        # ---- TD target ------------------------------------------------
-        (q1_t, q2_t), _ = self._target_chain.forward(next_states, na,
-                                                     save_acts=False)
+        # ---- TD-target twin + critic twin: independent chains of one
+        # shape, ONE launch (each alone fills 160 of 256 CUs) ------------
+        ((q1_t, q2_t), _), ((q1, q2), acts_c) = forward_pair(
+            (self._target_chain, (next_states, na), {"save_acts": False}),
+            (self._critic_chain, (states, actions), {}))
         fuse = self._fuse_tail
         # one launch for TD target + loss fwd + dq (its grid covers the
         # batch in <= 32 blocks); a larger batch keeps the three launches
@@ -608,7 +610,6 @@ class SACEngine:
                                  la_det, T, self.gamma, self.reward_scale)
 
         # ---- critic loss + manual backward ---------------------------
-        (q1, q2), acts_c = self._critic_chain.forward(states, actions)
         if fuse_loss:
             closs, dy = ext.critic_td_loss(
                 rewards, dones, q1_t, q2_t, nlp, q1, q2, states, la_det, T,

@@ -34,6 +34,7 @@
 #include <ATen/hip/HIPContext.h>
 #include <c10/hip/HIPStream.h>
 
+#include <algorithm>
 #include <vector>
 
 namespace chain {
@@ -94,16 +95,21 @@ __device__ __forceinline__ bf16x8 load_bfrag(const u16* __restrict__ w,
   return bf16x8{};
 }
 
-template <int RM>
-__global__ __launch_bounds__(NTHR) void k_bf16_chain_fwd(
+// The whole forward chain of ONE (row tile, group) workgroup; shared by
+// the single launch and the pair launch below.  PACKED_ONLY compiles the
+// k-loop down to the fragment-packed loader (every d.wp[li] must be set):
+// without the two raw-weight loaders the RM=1 body fits 128 VGPRs, i.e.
+// two workgroups per CU.
+template <int RM, bool PACKED_ONLY>
+__device__ __forceinline__ void chain_fwd_body(
     const void* __restrict__ x1, const void* __restrict__ x2,
     int C1, int C2, int x1f, int x2f, int rowcat, int M1,
     u16* __restrict__ xsave,
-    ChainFwdDesc d, void* __restrict__ y, int M, int out_f32) {
+    const ChainFwdDesc& d, void* __restrict__ y, int M, int out_f32,
+    int tile, int g) {
   constexpr int TMv = 16 * RM;
   __shared__ u16 sa[2][TMv][CPAD];
-  const int g = blockIdx.z;
-  const int m0 = blockIdx.x * TMv;
+  const int m0 = tile * TMv;
   const int tid = threadIdx.x;
   const int lane = tid & 63, wid = tid >> 6;
   const int fi = lane & 15, fk = lane >> 4;
@@ -223,7 +229,7 @@ __global__ __launch_bounds__(NTHR) void k_bf16_chain_fwd(
         }                                                                 \
       }
 
-      if (d.wp[li] != nullptr) {
+      if (PACKED_ONLY || d.wp[li] != nullptr) {
         // FRAGMENT-PACKED path: every load is wp + base + ks*512 +
         // lane*8 — one contiguous 1 KiB line per wave (TA cost 1/instr
         // instead of 16), zero-padding baked in (no guards, covers odd
@@ -389,6 +395,66 @@ __global__ __launch_bounds__(NTHR) void k_bf16_chain_fwd(
       K = N;
     }
   }
+}
+
+template <int RM>
+__global__ __launch_bounds__(NTHR) void k_bf16_chain_fwd(
+    const void* __restrict__ x1, const void* __restrict__ x2,
+    int C1, int C2, int x1f, int x2f, int rowcat, int M1,
+    u16* __restrict__ xsave,
+    ChainFwdDesc d, void* __restrict__ y, int M, int out_f32) {
+  chain_fwd_body<RM, false>(x1, x2, C1, C2, x1f, x2f, rowcat, M1, xsave, d,
+                            y, M, out_f32, blockIdx.x, blockIdx.z);
+}
+
+// ---------------------------------------------------------------------------
+// PAIR launch: two INDEPENDENT forward chains in one kernel.  One chain at
+// the flagship shape is 160 workgroups at one workgroup per CU (186
+// VGPRs), so a launch leaves 96 of 256 CUs empty for its whole ~25 us;
+// the TD-target twin and the critic twin of segment 1 read nothing the
+// other writes.  blockIdx.y selects the job, blockIdx.x its row tile,
+// blockIdx.z its group; the grid spans the larger of the two jobs in x
+// and z, surplus blocks leave before the first barrier.  The jobs share
+// nothing but the launch: shapes, dtypes, concat mode, layer count and
+// save_acts may all differ.  Packed weights are required (PACKED_ONLY);
+// RM=1 is bounded to 4 waves/SIMD so two workgroups (2 x 49,664 B LDS)
+// share a CU and all 320 flagship workgroups are resident at once.
+// ---------------------------------------------------------------------------
+struct ChainFwdJob {
+  const void* x1;
+  const void* x2;
+  u16* xsave;         // null = don't save the bf16 input
+  void* y;
+  ChainFwdDesc d;
+  int C1, C2, x1f, x2f, rowcat, M1, M, out_f32, G;
+};
+
+struct ChainFwdPair {
+  ChainFwdJob j[2];
+};
+
+template <int RM>
+__device__ __forceinline__ void chain_fwd_pair_block(const ChainFwdPair& p) {
+  // blockIdx.y is wave-uniform: the job's fields come in by scalar loads
+  // from the kernel arguments, like d.w[li] in the body
+  const ChainFwdJob& jb = p.j[blockIdx.y];
+  const int tile = blockIdx.x, g = blockIdx.z;
+  if (tile * (16 * RM) >= jb.M || g >= jb.G) return;   // block-uniform
+  chain_fwd_body<RM, true>(jb.x1, jb.x2, jb.C1, jb.C2, jb.x1f, jb.x2f,
+                           jb.rowcat, jb.M1, jb.xsave, jb.d, jb.y, jb.M,
+                           jb.out_f32, tile, g);
+}
+
+template <int RM>
+__global__ __launch_bounds__(NTHR) void k_bf16_chain_fwd_pair(
+    ChainFwdPair p) {
+  chain_fwd_pair_block<RM>(p);
+}
+
+template <>
+__global__ __launch_bounds__(NTHR, 4) void k_bf16_chain_fwd_pair<1>(
+    ChainFwdPair p) {
+  chain_fwd_pair_block<1>(p);
 }
 
 // ---------------------------------------------------------------------------
@@ -941,23 +1007,18 @@ static std::vector<torch::Tensor> mlp_chain_dx_bf16(
   return out;
 }
 
-// ---------------------------------------------------------------------------
-// Host binding: [y, x_bf16, act_0, ..., act_{L-2}] = mlp_chain_fwd_bf16(
-//     x1, x2_or_empty, ws, bs, act_last, G, out_f32, rm=0, rowcat=0,
-//     save_acts=1)
-// ws[i]: bf16 [G*N_i, K_i] (or [N,K] / [G,N,K]); bs[i]: f32 [G*N_i].
-// Inputs fp32 or bf16, 2-D [M, C]; x2 may be an empty tensor.  x_bf16 is
-// the converted (concatenated) input, so the backward consumes the same
-// activation list the per-layer path produced.  rm: 0 = auto (by M),
-// 1/2 = force 16/32 rows per workgroup.  rowcat=1 stacks x1/x2 over ROWS
-// (equal widths; M = M1+M2) instead of columns.  save_acts=0 skips the
-// intermediate-activation writes (no-grad forwards, e.g. TD target).
-// ---------------------------------------------------------------------------
-static std::vector<torch::Tensor> mlp_chain_fwd_bf16(
-    torch::Tensor x1, torch::Tensor x2, std::vector<torch::Tensor> ws,
-    std::vector<torch::Tensor> bs, long act_last, long G, long out_f32,
-    long rm, long rowcat, long save_acts,
-    std::vector<torch::Tensor> wps) {
+// Checks one forward chain's arguments, allocates its outputs into `out`
+// (the binding's return format) and fills the kernel-side job.  `pair`:
+// the pair launch's two differences — a packed buffer is REQUIRED for
+// every layer, and a save_acts=0 job gets no bf16 input copy (out[1] is
+// an empty tensor; nobody reads a no-grad forward's saved input).
+static ChainFwdJob make_fwd_job(
+    torch::Tensor x1, torch::Tensor x2,
+    const std::vector<torch::Tensor>& ws,
+    const std::vector<torch::Tensor>& bs, long act_last, long G,
+    long out_f32, long rowcat, long save_acts,
+    const std::vector<torch::Tensor>& wps, bool pair,
+    std::vector<torch::Tensor>& keep, std::vector<torch::Tensor>& out) {
   const int L = (int)ws.size();
   TORCH_CHECK(L >= 1 && L <= 6 && (int)bs.size() == L);
   TORCH_CHECK(wps.empty() || (int)wps.size() == L);
@@ -987,12 +1048,19 @@ static std::vector<torch::Tensor> mlp_chain_fwd_bf16(
   const long C1 = x1c.size(1), C2 = has2 ? x2c.size(1) : 0;
   const long K0 = rowcat ? C1 : C1 + C2;
   TORCH_CHECK(K0 <= CMAX, "chain fwd: input width must be <= ", CMAX);
+  TORCH_CHECK(!pair || (int)wps.size() == L,
+              "chain fwd pair: packed weights are required for every layer");
+  keep.push_back(x1c);
+  keep.push_back(x2c);
 
-  ChainFwdDesc d{};
+  ChainFwdJob job{};
+  ChainFwdDesc& d = job.d;
   d.L = L;
-  std::vector<torch::Tensor> keep, out;
   auto bopts = x1c.options().dtype(torch::kBFloat16);
-  auto xsave = torch::empty({M, K0}, bopts);
+  const bool save_x = !pair || save_acts;
+  auto xsave = save_x ? torch::empty({M, K0}, bopts)
+                      : torch::empty({0}, bopts);
+  out.clear();
   out.resize(2);
   out[1] = xsave;
   long K = K0;
@@ -1017,6 +1085,8 @@ static std::vector<torch::Tensor> mlp_chain_fwd_bf16(
       d.wp[i] = (const u16*)wps[i].data_ptr();
       keep.push_back(wps[i]);
     }
+    TORCH_CHECK(!pair || d.wp[i] != nullptr,
+                "chain fwd pair: no packed weights for layer ", i);
     d.b[i] = bc.data_ptr<float>();
     d.N[i] = (int)N;
     d.act[i] = (i == L - 1) ? (int)act_last : 1;
@@ -1034,6 +1104,43 @@ static std::vector<torch::Tensor> mlp_chain_fwd_bf16(
   auto y = G == 1 ? torch::empty({M, (long)d.N[L - 1]}, yopts)
                   : torch::empty({G, M, (long)d.N[L - 1]}, yopts);
   out[0] = y;
+  job.x1 = x1c.data_ptr();
+  job.x2 = has2 ? x2c.data_ptr() : nullptr;
+  job.xsave = save_x ? (u16*)xsave.data_ptr() : nullptr;
+  job.y = y.data_ptr();
+  job.C1 = (int)C1;
+  job.C2 = (int)C2;
+  job.x1f = x1f ? 1 : 0;
+  job.x2f = x2f ? 1 : 0;
+  job.rowcat = (int)rowcat;
+  job.M1 = (int)M1;
+  job.M = (int)M;
+  job.out_f32 = (int)out_f32;
+  job.G = (int)G;
+  return job;
+}
+
+// ---------------------------------------------------------------------------
+// Host binding: [y, x_bf16, act_0, ..., act_{L-2}] = mlp_chain_fwd_bf16(
+//     x1, x2_or_empty, ws, bs, act_last, G, out_f32, rm=0, rowcat=0,
+//     save_acts=1)
+// ws[i]: bf16 [G*N_i, K_i] (or [N,K] / [G,N,K]); bs[i]: f32 [G*N_i].
+// Inputs fp32 or bf16, 2-D [M, C]; x2 may be an empty tensor.  x_bf16 is
+// the converted (concatenated) input, so the backward consumes the same
+// activation list the per-layer path produced.  rm: 0 = auto (by M),
+// 1/2 = force 16/32 rows per workgroup.  rowcat=1 stacks x1/x2 over ROWS
+// (equal widths; M = M1+M2) instead of columns.  save_acts=0 skips the
+// intermediate-activation writes (no-grad forwards, e.g. TD target).
+// ---------------------------------------------------------------------------
+static std::vector<torch::Tensor> mlp_chain_fwd_bf16(
+    torch::Tensor x1, torch::Tensor x2, std::vector<torch::Tensor> ws,
+    std::vector<torch::Tensor> bs, long act_last, long G, long out_f32,
+    long rm, long rowcat, long save_acts,
+    std::vector<torch::Tensor> wps) {
+  std::vector<torch::Tensor> keep, out;
+  const ChainFwdJob j = make_fwd_job(x1, x2, ws, bs, act_last, G, out_f32,
+                                     rowcat, save_acts, wps, false, keep,
+                                     out);
   // RM=1 measured faster at every bench shape (RM=2 halves the L2
   // weight re-read but also halves the workgroups, and these chains are
   // occupancy/latency-bound, not L2-bound — tools/validate_chain_fwd.py
@@ -1042,23 +1149,55 @@ static std::vector<torch::Tensor> mlp_chain_fwd_bf16(
   int use_rm = (int)rm;
   if (use_rm == 0) use_rm = 1;
   const int TMv = 16 * use_rm;
-  dim3 grid((M + TMv - 1) / TMv, 1, G);
+  dim3 grid((j.M + TMv - 1) / TMv, 1, j.G);
   if (use_rm == 2)
     hipLaunchKernelGGL(k_bf16_chain_fwd<2>, grid, dim3(NTHR), 0,
-                       cur_stream3(), x1c.data_ptr(),
-                       has2 ? x2c.data_ptr() : nullptr, (int)C1, (int)C2,
-                       (int)(x1f ? 1 : 0), (int)(x2f ? 1 : 0),
-                       (int)rowcat, (int)M1,
-                       (u16*)xsave.data_ptr(), d,
-                       y.data_ptr(), (int)M, (int)out_f32);
+                       cur_stream3(), j.x1, j.x2, j.C1, j.C2, j.x1f, j.x2f,
+                       j.rowcat, j.M1, j.xsave, j.d, j.y, j.M, j.out_f32);
   else
     hipLaunchKernelGGL(k_bf16_chain_fwd<1>, grid, dim3(NTHR), 0,
-                       cur_stream3(), x1c.data_ptr(),
-                       has2 ? x2c.data_ptr() : nullptr, (int)C1, (int)C2,
-                       (int)(x1f ? 1 : 0), (int)(x2f ? 1 : 0),
-                       (int)rowcat, (int)M1,
-                       (u16*)xsave.data_ptr(), d,
-                       y.data_ptr(), (int)M, (int)out_f32);
+                       cur_stream3(), j.x1, j.x2, j.C1, j.C2, j.x1f, j.x2f,
+                       j.rowcat, j.M1, j.xsave, j.d, j.y, j.M, j.out_f32);
+  return out;
+}
+
+// ---------------------------------------------------------------------------
+// Host binding: (outs_a, outs_b) = mlp_chain_fwd_pair_bf16(
+//     <the arguments of mlp_chain_fwd_bf16 for job a>, <... for job b>, rm)
+// Two independent forward chains in ONE k_bf16_chain_fwd_pair launch; each
+// output list has the single binding's format and bits.  Both jobs need a
+// packed buffer for every layer.  A save_acts=0 job's bf16 input copy is
+// neither allocated nor written (its slot is an empty tensor).  rm: 0/1 =
+// 16-row tiles, 2 = 32-row tiles.
+// ---------------------------------------------------------------------------
+static std::vector<std::vector<torch::Tensor>> mlp_chain_fwd_pair_bf16(
+    torch::Tensor a_x1, torch::Tensor a_x2, std::vector<torch::Tensor> a_ws,
+    std::vector<torch::Tensor> a_bs, long a_act_last, long a_G,
+    long a_out_f32, long a_rowcat, long a_save_acts,
+    std::vector<torch::Tensor> a_wps,
+    torch::Tensor b_x1, torch::Tensor b_x2, std::vector<torch::Tensor> b_ws,
+    std::vector<torch::Tensor> b_bs, long b_act_last, long b_G,
+    long b_out_f32, long b_rowcat, long b_save_acts,
+    std::vector<torch::Tensor> b_wps, long rm) {
+  TORCH_CHECK(rm >= 0 && rm <= 2, "chain fwd pair: rm must be 0, 1 or 2");
+  TORCH_CHECK(a_x1.device() == b_x1.device(),
+              "chain fwd pair: both jobs must be on one device");
+  std::vector<torch::Tensor> keep;
+  std::vector<std::vector<torch::Tensor>> out(2);
+  ChainFwdPair p;
+  p.j[0] = make_fwd_job(a_x1, a_x2, a_ws, a_bs, a_act_last, a_G, a_out_f32,
+                        a_rowcat, a_save_acts, a_wps, true, keep, out[0]);
+  p.j[1] = make_fwd_job(b_x1, b_x2, b_ws, b_bs, b_act_last, b_G, b_out_f32,
+                        b_rowcat, b_save_acts, b_wps, true, keep, out[1]);
+  const int TMv = rm == 2 ? 32 : 16;
+  const int tiles = (std::max(p.j[0].M, p.j[1].M) + TMv - 1) / TMv;
+  dim3 grid(tiles, 2, std::max(p.j[0].G, p.j[1].G));
+  if (rm == 2)
+    hipLaunchKernelGGL(k_bf16_chain_fwd_pair<2>, grid, dim3(NTHR), 0,
+                       cur_stream3(), p);
+  else
+    hipLaunchKernelGGL(k_bf16_chain_fwd_pair<1>, grid, dim3(NTHR), 0,
+                       cur_stream3(), p);
   return out;
 }
 
@@ -1079,4 +1218,15 @@ void register_chain(pybind11::module_& m) {
         pybind11::arg("out_f32"), pybind11::arg("rm") = 0,
         pybind11::arg("rowcat") = 0, pybind11::arg("save_acts") = 1,
         pybind11::arg("wps") = std::vector<torch::Tensor>{});
+  m.def("mlp_chain_fwd_pair_bf16", &chain::mlp_chain_fwd_pair_bf16,
+        pybind11::arg("a_x1"), pybind11::arg("a_x2"), pybind11::arg("a_ws"),
+        pybind11::arg("a_bs"), pybind11::arg("a_act_last"),
+        pybind11::arg("a_G"), pybind11::arg("a_out_f32"),
+        pybind11::arg("a_rowcat"), pybind11::arg("a_save_acts"),
+        pybind11::arg("a_wps"),
+        pybind11::arg("b_x1"), pybind11::arg("b_x2"), pybind11::arg("b_ws"),
+        pybind11::arg("b_bs"), pybind11::arg("b_act_last"),
+        pybind11::arg("b_G"), pybind11::arg("b_out_f32"),
+        pybind11::arg("b_rowcat"), pybind11::arg("b_save_acts"),
+        pybind11::arg("b_wps"), pybind11::arg("rm") = 0);
 }

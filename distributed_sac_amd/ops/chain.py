@@ -104,6 +104,14 @@ class ManualChain:
     def _youts(self, acts):
         return list(acts[1:len(self.ws16)]) + [self._empty]
 
+    def _fwd_args(self, x1, x2=None, *, rowcat=False, save_acts=True,
+                  out_f32=True, act_last=0):
+        """forward()'s arguments as one job of the pair binding."""
+        return (x1, x2 if x2 is not None else x1.new_empty(0),
+                self.ws16, [b.contiguous() for b in self.bs],
+                int(act_last), self.G, 1 if out_f32 else 0,
+                1 if rowcat else 0, 1 if save_acts else 0, self.fwd_frag)
+
     @torch.no_grad()
     def forward(self, x1, x2=None, *, rowcat=False, save_acts=True,
                 out_f32=True, act_last=0):
@@ -186,6 +194,29 @@ class ManualChain:
         ext.dwdb_grouped_arena(list(outs[:n]), list(acts[:n]), arena,
                                self.w_offs, self.b_offs, self.G, S, chunk)
         return dx0
+
+
+def use_pair_fwd() -> bool:
+    """Two independent forward chains in one launch (forward_pair).
+    DSAC_PAIR_FWD=0 restores the two separate launches."""
+    return os.environ.get("DSAC_PAIR_FWD", "1") != "0"
+
+
+@torch.no_grad()
+def forward_pair(a, b):
+    """``chain.forward(*args, **kwargs)`` of two INDEPENDENT chains, each
+    given as ``(chain, args, kwargs)``; returns the two results.  With both
+    chains on the chain kernels this is one k_bf16_chain_fwd_pair launch
+    (same bits; a ``save_acts=False`` job's acts[0] comes back empty),
+    otherwise the two forward calls in the given order.  DSAC_PAIR_RM=2
+    selects 32-row tiles (measurement only)."""
+    (ca, args_a, kw_a), (cb, args_b, kw_b) = a, b
+    if not (ca.chain_mode and cb.chain_mode and use_pair_fwd()):
+        return ca.forward(*args_a, **kw_a), cb.forward(*args_b, **kw_b)
+    rm = 2 if os.environ.get("DSAC_PAIR_RM", "1") == "2" else 1
+    outs = native().mlp_chain_fwd_pair_bf16(
+        *ca._fwd_args(*args_a, **kw_a), *cb._fwd_args(*args_b, **kw_b), rm)
+    return tuple((o[0], [o[1]] + list(o[2:])) for o in outs)
 
 
 def pack_chains(ext, entries: Sequence[Tuple[ManualChain, bool, bool]]):
