@@ -199,6 +199,8 @@ class CAREEngine(SACEngine):
         return Fops.squashed_gaussian(mu, log_std_raw, eps, self.actor.k)
 
     def update_tensors(self, batch: Dict[str, torch.Tensor]):
+        if "is_weights" in batch:
+            self._per_unsupported()
         if self._use_fused(batch["states"]):
             if self.degenerate_w and self.use_weighted_loss:
                 raise RuntimeError(

@@ -62,6 +62,12 @@ class SACEngine:
         self._graph = None
         self._eps_queue: Optional[list] = None  # test hook: deterministic eps
         self.ddp = None  # optional DataParallelGroup (set via attach_ddp)
+        # prioritized replay: the attached replay (attach_per) and what the
+        # last prioritized update left for the write-back
+        self._per = None
+        self.per_indices: Optional[torch.Tensor] = None
+        self.per_new_priorities: Optional[torch.Tensor] = None
+        self._per_zeroed = False
         self._build_models()
         self._build_optimizers()
 
@@ -361,6 +367,62 @@ class SACEngine:
             return Fops.gather_log_alpha(one_hots, self.log_alpha).exp().detach()
         return self.log_alpha.exp().detach()
 
+    # -- prioritized replay ----------------------------------------------
+    def _per_unsupported(self) -> None:
+        """Raise for the combinations prioritized replay does not cover."""
+        why = None
+        if self.variant == "care":
+            why = "CAREEngine has no prioritized-replay path"
+        elif self.ddp is not None and getattr(self.ddp, "enabled", True):
+            why = "not supported with a data-parallel group attached"
+        elif self.degenerate_w and self.use_weighted_loss:
+            why = "not defined for weighted_loss_mode='reference'"
+        elif self.device.type == "cuda" and self._use_fused(
+                self.log_alpha) and not (
+                getattr(self, "_bf16", False)
+                and os.environ.get("DSAC_NO_MANUAL", "0") != "1"):
+            why = ("on a GPU only the bf16 manual-backward path carries "
+                   "importance-sampling weights (not the fp32 fused path)")
+        if why is not None:
+            raise NotImplementedError(f"prioritized replay: {why}")
+
+    def attach_per(self, replay) -> None:
+        """Pair with a ``sampling="prioritized"`` replay: its per_alpha /
+        per_eps shape the new priorities, and every update of a batch that
+        carries ``is_weights`` writes them back with
+        ``replay.update_priorities`` (inside the graph when captured)."""
+        self._per_unsupported()
+        self._per = replay
+
+    def _per_params(self):
+        src = self._per if self._per is not None else self.cfg
+        return float(src.per_alpha), float(src.per_eps)
+
+    def per_write_back(self, replay) -> None:
+        """Feed the last prioritized update's new priorities to
+        ``replay``."""
+        replay.update_priorities(self.per_indices, self.per_new_priorities,
+                                 _zeroed=self._per_zeroed)
+        self._per_zeroed = False
+
+    def _critic_loss_per(self, states, actions, y, isn):
+        """Eager critic losses with normalised IS weights ``isn [B, 1]``
+        on the per-row squared errors (and on the task weights, if on);
+        also returns the two TD errors."""
+        if self.variant in ("sac", "vsac"):
+            q1 = self.local_critic_1(states, actions)
+            q2 = self.local_critic_2(states, actions)
+        else:
+            q1, q2 = self.local_critic(states, actions)
+        d1, d2 = y - q1, y - q2
+        wi = isn
+        if self.use_weighted_loss:
+            w = Fops.task_weights(states[:, -self.num_tasks:],
+                                  self.log_alpha.exp().detach())
+            wi = w.unsqueeze(-1) * isn
+        q_loss = (wi * d1 ** 2).mean() + (wi * d2 ** 2).mean()
+        return q_loss, d1.detach(), d2.detach()
+
     def update(self, batch: Dict[str, torch.Tensor]) -> Dict[str, float]:
         """One SAC gradient update; returns scalar metrics (syncs)."""
         out = self.update_tensors(batch)
@@ -373,7 +435,21 @@ class SACEngine:
 
         Order (identical to reference update/update_SAC): TD target →
         critic step → actor step → alpha step → Polyak.
+
+        A batch from a prioritized replay (keys ``is_weights``,
+        ``indices``) weights the critic loss with ``w / max w`` and leaves
+        the rows' new priorities in ``per_new_priorities``; with a replay
+        attached (:meth:`attach_per`) they are written back here.
         """
+        per = "is_weights" in batch
+        if per:
+            self._per_unsupported()
+        out = self._update_tensors(batch)
+        if per and self._per is not None:
+            self.per_write_back(self._per)
+        return out
+
+    def _update_tensors(self, batch):
         if self._use_fused(batch["states"]):
             if self.degenerate_w and self.use_weighted_loss:
                 raise RuntimeError(
@@ -398,7 +474,16 @@ class SACEngine:
                                alpha, self.gamma, self.reward_scale)
 
         # --- critic step ---------------------------------------------
-        if self.variant in ("sac", "vsac"):
+        if "is_weights" in batch:
+            from ..ops import torch_ref
+            w = batch["is_weights"].reshape(-1, 1)
+            q_loss, d1, d2 = self._critic_loss_per(states, actions, y,
+                                                   w / w.max())
+            self.per_indices = batch["indices"]
+            self.per_new_priorities = torch_ref.per_new_priorities(
+                d1, d2, *self._per_params())
+            self._per_zeroed = False
+        elif self.variant in ("sac", "vsac"):
             q_loss = (self.local_critic_1.cal_loss(states, actions, y)
                       + self.local_critic_2.cal_loss(states, actions, y))
         else:
@@ -610,7 +695,23 @@ class SACEngine:
                                  la_det, T, self.gamma, self.reward_scale)
 
         # ---- critic loss + manual backward ---------------------------
-        if fuse_loss:
+        if "is_weights" in batch:
+            if not fuse_loss:
+                raise NotImplementedError(
+                    "prioritized replay: the IS-weighted critic loss is "
+                    "the fused kernel only (B <= 8192, DSAC_FUSE_TAIL=1)")
+            # with a replay attached the kernel also zeroes the sampled
+            # leaves, the first step of the write-back that follows
+            prio = self._per.per_prio if self._per is not None else None
+            closs, dy, newp = ext.critic_td_loss_per(
+                rewards, dones, q1_t, q2_t, nlp, q1, q2, states, la_det, T,
+                int(use_w), self.gamma, self.reward_scale, self._loss_ws,
+                batch["is_weights"], *self._per_params(), prio,
+                batch["indices"] if prio is not None else None)
+            self.per_indices = batch["indices"]
+            self.per_new_priorities = newp
+            self._per_zeroed = prio is not None
+        elif fuse_loss:
             closs, dy = ext.critic_td_loss(
                 rewards, dones, q1_t, q2_t, nlp, q1, q2, states, la_det, T,
                 int(use_w), self.gamma, self.reward_scale, self._loss_ws)
@@ -841,6 +942,9 @@ class SACEngine:
         if self._use_krng and hasattr(replay, "attach_rng"):
             replay.attach_rng(self._rng_ctr)
         assert self.device.type == "cuda", "capture needs a GPU"
+        if getattr(replay, "sampling", None) == "prioritized":
+            # every captured update writes its new priorities back
+            self.attach_per(replay)
         self._graph_chunk = max(1, int(chunk))
         torch.cuda.synchronize(self.device)
         side = torch.cuda.Stream(self.device)
@@ -877,6 +981,10 @@ class SACEngine:
     # intermediates (activations, squash state) keep stable addresses.
     # ------------------------------------------------------------------
     def capture_dp(self, replay, batch_size: int, warmup_iters: int = 3):
+        if getattr(replay, "sampling", None) == "prioritized":
+            raise NotImplementedError(
+                "prioritized replay: not supported under data-parallel "
+                "capture")
         if self._use_krng and hasattr(replay, "attach_rng"):
             replay.attach_rng(self._rng_ctr)
         assert self.device.type == "cuda", "capture needs a GPU"

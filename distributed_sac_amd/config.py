@@ -98,7 +98,16 @@ class SACConfig:
     # independently.  "without_replacement": each shard's rows of a batch
     # are distinct, as the reference's random.sample.  See docs/PARITY.md
     # "replay sampling".
+    # "prioritized" (net-new, the reference has none): proportional
+    # prioritized replay with importance-sampling weights; per_alpha is the
+    # priority exponent, per_beta the IS exponent (annealed linearly to 1.0
+    # over per_beta_anneal_steps grad steps; 0 = constant), per_eps the
+    # floor added to the TD error.
     replay_sampling: str = "replace"
+    per_alpha: float = 0.6
+    per_beta: float = 0.4
+    per_beta_anneal_steps: int = 0
+    per_eps: float = 1e-6
     # CARE-only block (reference cfg "encoder"):
     encoder: Optional[Dict[str, Any]] = None
     use_modified_care: bool = False
@@ -123,6 +132,13 @@ class SACConfig:
         if "replay_sampling" in self.raw or self.replay_sampling != "replace":
             return self.replay_sampling
         return None
+
+    @property
+    def per_kwargs(self) -> Dict[str, Any]:
+        """The prioritized-replay settings as ShardedReplay arguments."""
+        return {"per_alpha": self.per_alpha, "per_beta": self.per_beta,
+                "per_beta_anneal_steps": self.per_beta_anneal_steps,
+                "per_eps": self.per_eps}
 
     @property
     def k(self) -> float:
@@ -167,10 +183,21 @@ class SACConfig:
             c.weighted_loss_mode = str(cfg["weighted_loss_mode"])
         if "replay_sampling" in cfg:
             c.replay_sampling = str(cfg["replay_sampling"])
-            if c.replay_sampling not in ("replace", "without_replacement"):
+            if c.replay_sampling not in ("replace", "without_replacement",
+                                         "prioritized"):
                 raise ValueError(
-                    "replay_sampling must be 'replace' or "
-                    f"'without_replacement', got {c.replay_sampling!r}")
+                    "replay_sampling must be 'replace', "
+                    "'without_replacement' or 'prioritized', "
+                    f"got {c.replay_sampling!r}")
+        if any(k in cfg for k in ("per_alpha", "per_beta",
+                                  "per_beta_anneal_steps", "per_eps")):
+            from .replay.gpu_replay import check_per_params
+            for k, v in check_per_params(
+                    **{k: cfg.get(k) for k in (
+                        "per_alpha", "per_beta", "per_beta_anneal_steps",
+                        "per_eps")}).items():
+                if k in cfg:
+                    setattr(c, k, v)
         if "use_modified_care" in cfg:
             c.use_modified_care = bool(cfg["use_modified_care"])
         if "encoder" in cfg:

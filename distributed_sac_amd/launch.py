@@ -44,7 +44,8 @@ def main():
     ap.add_argument("--env", default=None,
                     help="env name for make_env (default: synthetic)")
     ap.add_argument("--sampling", default=None,
-                    choices=["replace", "without_replacement"],
+                    choices=["replace", "without_replacement",
+                             "prioritized"],
                     help="replay minibatch draw (default: the cfg's "
                          "replay_sampling, else DSAC_SAMPLING, else replace)")
     # eval mode

@@ -1556,6 +1556,474 @@ __global__ __launch_bounds__(256) void k_critic_td_loss(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Prioritized replay (opt-in; docs/KERNELS.md "Prioritized replay"; the exact
+// oracle is torch_ref.per_*).  Leaves prio[T, cap] (0 = never written), block
+// sums bsum[T, nb] over PER_BLOCK leaves each, total[T], max_prio[T].  Sums
+// are only ever RECOMPUTED from what they cover, in one fixed order, so
+// "bsum = fixed-order sum of its leaves, total = fixed-order sum of the
+// shard's bsum" holds bit for bit.
+//
+// The fixed order over n values, by one 256-thread block: thread i adds
+// v[i], v[i + 256], v[i + 512], ... in that order, then the 256 partials
+// fold by halves (i with i + 128, then + 64, ... + 1).
+// ---------------------------------------------------------------------------
+constexpr int PER_BLOCK = 1024;
+
+// fold of 256 per-thread partials; the result is valid in thread 0.  Every
+// thread of the block must call it.
+__device__ __forceinline__ float per_fold256(float acc, float* s) {
+  const int tid = threadIdx.x;
+  __syncthreads();   // a previous fold may still be reading s
+  s[tid] = acc;
+  __syncthreads();
+  float v = 0.f;
+  if (tid < 64) {
+    v = (s[tid] + s[tid + 128]) + (s[tid + 64] + s[tid + 192]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  }
+  return v;
+}
+
+// The same fixed order by ONE wave, without LDS: lane l forms the partials
+// l, l + 64, l + 128, l + 192 itself, folds them ((l, l + 128) and
+// (l + 64, l + 192) are the first two halvings), then the wave folds by
+// halves.  The result is valid in lane 0.
+template <bool VOLATILE>
+__device__ __forceinline__ float per_wave_fixed_sum(const float* p, int n,
+                                                    int lane) {
+  float a[4] = {0.f, 0.f, 0.f, 0.f};
+  // 1024 values at a time: 16 independent loads per lane (values past n
+  // read as 0, which adds exactly), then the adds in the fixed order
+  for (int s0 = 0; s0 < n; s0 += 1024) {
+    float vv[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int k = s0 + r * 256 + q * 64 + lane;
+        vv[r][q] = k >= n ? 0.f
+            : (VOLATILE ? ((const volatile float*)p)[k] : p[k]);
+      }
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) a[q] += vv[r][q];
+  }
+  float v = (a[0] + a[2]) + (a[1] + a[3]);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+
+// Non-blocking "last block finalises": every block counts itself in after
+// its bsum stores; the last one recomputes total[t0 .. t0 + nt) from the
+// block sums (one wave per shard) and resets the ticket.  Every thread of
+// the block must call it; any block size that is a multiple of 64.
+__device__ __forceinline__ void per_finish_totals(
+    const float* bsum, float* total, unsigned* ticket, int nb, int t0, int nt,
+    int* s_last) {
+  const int tid = threadIdx.x;
+  __syncthreads();
+  if (tid == 0) {
+    __threadfence();
+    const unsigned old = atomicAdd(ticket, 1u);
+    *s_last = (old == gridDim.x * gridDim.y - 1u);
+    if (*s_last) {
+      *ticket = 0u;
+      __threadfence();
+    }
+  }
+  __syncthreads();
+  if (!*s_last) return;
+  const int lane = tid & 63;
+  for (int t = t0 + (tid >> 6); t < t0 + nt; t += (int)(blockDim.x >> 6)) {
+    const float v = per_wave_fixed_sum<true>(bsum + (long)t * nb, nb, lane);
+    if (lane == 0) total[t] = v;
+  }
+}
+
+// Hillis-Steele inclusive scan over the wave (lane l adds lane l - off for
+// off = 1, 2, 4, ... 32): the association torch_ref._hs_scan64 reproduces.
+__device__ __forceinline__ float per_wave_scan(float v, int lane) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const float o = __shfl_up(v, off, 64);
+    if (lane >= off) v = __fadd_rn(v, o);
+  }
+  return v;
+}
+
+// First k in [0, n) with p[k] > 0 whose inclusive prefix sum exceeds x, by
+// the whole wave: chunks of 64 coalesced loads, a wave scan each, a running
+// base.  Returns -1 if there is none; then last_nz is the last k with
+// p[k] > 0 (-1: none).  On a hit, excl is the prefix before k and val p[k].
+// All arguments and results are wave-uniform.
+__device__ __forceinline__ int per_wave_search(const float* p, int n, float x,
+                                               int lane, float& excl,
+                                               float& val, int& last_nz) {
+  float base = 0.f;
+  last_nz = -1;
+  // 16 chunks are loaded at once (independent loads, one memory latency
+  // instead of one per chunk), then scanned in order
+  for (int s0 = 0; s0 < n; s0 += 16 * 64) {
+    float vv[16];
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+      const int k = s0 + c * 64 + lane;
+      vv[c] = k < n ? p[k] : 0.f;
+    }
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+      const int c0 = s0 + c * 64;
+      if (c0 >= n) break;
+      const float v = vv[c];
+      const float incl = __fadd_rn(base, per_wave_scan(v, lane));
+      const unsigned long long nz = __ballot(v > 0.f);
+      const unsigned long long hit = __ballot(incl > x && v > 0.f);
+      if (hit != 0ull) {
+        const int l = __ffsll((long long)hit) - 1;
+        const float prev = __shfl(incl, l > 0 ? l - 1 : 0, 64);
+        excl = l > 0 ? prev : base;
+        val = __shfl(v, l, 64);
+        return c0 + l;
+      }
+      if (nz != 0ull) last_nz = c0 + 63 - __clzll((long long)nz);
+      base = __shfl(incl, 63, 64);
+    }
+  }
+  return -1;
+}
+
+// K12d: stratified PROPORTIONAL draw + gather.  One wave per batch row, as
+// k_replay_sample; the row index is wave-uniform (readfirstlane), so the two
+// searches cannot diverge.  Row j of shard t draws from the j-th of `per`
+// equal slices of the shard's priority mass:
+//   x = (float(j) + u) * (total_t / float(per))      (fp32, RN, this order)
+// with u the uniform k_replay_sample derives for batch row i.  It gathers
+// the first row whose inclusive prefix sum exceeds x: first the block (scan
+// of bsum), then, with x minus the prefix before that block, the leaf.  When
+// rounding leaves no such block / leaf, the last one with a non-zero sum /
+// priority is taken.  Raw IS weight (n_t * p / total_t) ** -beta.  An empty
+// shard yields row 0 and weight 1.
+__global__ __launch_bounds__(256) void k_replay_sample_per(
+    const float* __restrict__ states, const float* __restrict__ actions,
+    const float* __restrict__ rewards, const float* __restrict__ next_states,
+    const float* __restrict__ dones, const float* __restrict__ sizes,
+    const float* __restrict__ prio, const float* __restrict__ bsum,
+    const float* __restrict__ total, const float* __restrict__ beta,
+    const long long* __restrict__ rng, float* __restrict__ o_states,
+    float* __restrict__ o_actions, float* __restrict__ o_rewards,
+    float* __restrict__ o_next_states, float* __restrict__ o_dones,
+    long long* __restrict__ idx_out, float* __restrict__ w_out, int B, int T,
+    int per, long cap, int nb, int Ds, int Da) {
+  const int i = __builtin_amdgcn_readfirstlane(
+      (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));
+  const int lane = threadIdx.x & 63;
+  if (i >= B) return;
+  const int t = min(i / per, T - 1);
+  const int j = i - t * per;
+  const unsigned long long c = (unsigned long long)rng[0];
+  float u = dsac_u01(dsac_sm64(c * 0x100000001ull
+                               + (unsigned long long)i * 2ull + 0x2ull));
+  u = u < 1.f ? u : 0.99999994f;
+  const float n = fminf(sizes[t], (float)cap);
+  const float tot = total[t];
+  long idx = 0;
+  float w = 1.f;
+  if (n >= 1.f && tot > 0.f) {
+    const float x = __fmul_rn(__fadd_rn((float)j, u),
+                              __fdiv_rn(tot, (float)per));
+    float excl = 0.f, val = 0.f;
+    int last = -1;
+    int b = per_wave_search(bsum + (long)t * nb, nb, x, lane, excl, val,
+                            last);
+    float xr;
+    if (b < 0) {
+      b = last > 0 ? last : 0;
+      xr = INFINITY;
+    } else {
+      xr = __fsub_rn(x, excl);
+    }
+    const long base = (long)b * PER_BLOCK;
+    const int nl = (int)(cap - base < PER_BLOCK ? cap - base : PER_BLOCK);
+    const float* lp = prio + (long)t * cap + base;
+    int l = per_wave_search(lp, nl, xr, lane, excl, val, last);
+    if (l < 0) {
+      l = last > 0 ? last : 0;
+      val = lp[l];
+    }
+    idx = base + l;
+    if (val > 0.f)
+      w = powf(__fdiv_rn(__fmul_rn(n, val), tot), -beta[0]);
+  }
+  const long src = (long)t * cap + idx;
+  for (int k = lane; k < Ds; k += 64) {
+    o_states[(long)i * Ds + k] = states[src * Ds + k];
+    o_next_states[(long)i * Ds + k] = next_states[src * Ds + k];
+  }
+  for (int k = lane; k < Da; k += 64)
+    o_actions[(long)i * Da + k] = actions[src * Da + k];
+  if (lane == 0) {
+    o_rewards[i] = rewards[src];
+    o_dones[i] = dones[src];
+    idx_out[i] = src;
+    w_out[i] = w;
+  }
+}
+
+// k_critic_td_loss with importance-sampling weights: every per-row squared
+// error and dq coefficient is multiplied by isw[i] / max_j isw[j] (each block
+// recomputes the batch maximum: <= 8192 floats, order-independent).  The
+// task-weight normaliser (out[2], out[5]) is the unweighted one, so equal
+// IS weights reproduce k_critic_td_loss bit for bit.  Also writes each row's
+// new priority (0.5 (|y - q1| + |y - q2|) + eps) ** alpha and, given the
+// leaves and the rows' flat indices, zeroes the sampled leaves so that
+// k_per_max can max the new values in.
+__global__ __launch_bounds__(256) void k_critic_td_loss_per(
+    const float* __restrict__ r, const float* __restrict__ d,
+    const float* __restrict__ q1t, const float* __restrict__ q2t,
+    const float* __restrict__ nlp, const float* __restrict__ q1,
+    const float* __restrict__ q2, const float* __restrict__ onehot,
+    const float* __restrict__ log_alpha, float* __restrict__ out,
+    float* __restrict__ ws, unsigned short* __restrict__ dq,
+    int B, int T, int oh_stride, int use_w, float gamma, float rs,
+    const float* __restrict__ isw, float* __restrict__ newp,
+    float* __restrict__ prio, const long long* __restrict__ idx, long n_prio,
+    float per_alpha, float per_eps) {
+  __shared__ float part[3][4];
+  __shared__ float smw[32];
+  __shared__ float wpart[32][4];
+  __shared__ float s_fin[32 * 3];
+  __shared__ float s_max[4];
+  __shared__ int s_last;
+  const int tid = threadIdx.x;
+  const int i = blockIdx.x * 256 + tid;
+  const long ic = i < B ? i : B - 1;
+  const float rv = r[ic], dv = d[ic], q1tv = q1t[ic], q2tv = q2t[ic];
+  const float lpv = nlp[ic], q1v = q1[ic], q2v = q2[ic];
+  const float iswv = isw[ic];
+  float m = 0.f;
+  for (int k = tid; k < B; k += 256) m = fmaxf(m, isw[k]);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+    m = fmaxf(m, __shfl_xor(m, off, 64));
+  if ((tid & 63) == 0) s_max[tid >> 6] = m;
+  __syncthreads();
+  const float wmax = fmaxf(fmaxf(s_max[0], s_max[1]),
+                           fmaxf(s_max[2], s_max[3]));
+  const float isn = wmax > 0.f ? iswv / wmax : 1.f;
+  int t_i = 0;
+  float wsum = 1.f;
+  if (use_w) {
+    fill_task_weights(smw, log_alpha, T);
+    __syncthreads();
+    wsum = batch_weight_sum(smw, onehot, wpart, B, T, oh_stride,
+                            (int)gridDim.x, t_i);
+  } else {
+    t_i = task_of_row(onehot, ic, oh_stride, T);
+  }
+  float s_l1 = 0.f, s_l2 = 0.f, s_w = 0.f;
+  if (i < B) {
+    const float alpha = __expf(log_alpha[t_i]);
+    const float y = td_target_value(rs, rv, gamma, dv, fminf(q1tv, q2tv),
+                                    alpha, lpv);
+    const float w_raw = use_w ? smw[t_i] : 1.f;
+    s_w += w_raw;
+    const float wi = w_raw * isn;
+    const float d1 = y - q1v, d2 = y - q2v;
+    s_l1 += wi * d1 * d1;
+    s_l2 += wi * d2 * d2;
+    const float coeff = (use_w ? wi / wsum : isn) / (float)B;
+    dq[i] = f32_bf16_rne_d(coeff * -2.f * (y - q1v));
+    dq[B + i] = f32_bf16_rne_d(coeff * -2.f * (y - q2v));
+    newp[i] = powf(0.5f * (fabsf(d1) + fabsf(d2)) + per_eps, per_alpha);
+    if (prio != nullptr) {
+      const long flat = idx[i];
+      if (flat >= 0 && flat < n_prio) prio[flat] = 0.f;
+    }
+  }
+  s_l1 = wave_sum64(s_l1); s_l2 = wave_sum64(s_l2); s_w = wave_sum64(s_w);
+  const int wid = tid >> 6;
+  if ((tid & 63) == 0) {
+    part[0][wid] = s_l1; part[1][wid] = s_l2; part[2][wid] = s_w;
+  }
+  __syncthreads();
+  float* slots = ws + 1;
+  if (tid == 0) {
+    slots[blockIdx.x * 3 + 0] =
+        part[0][0] + part[0][1] + part[0][2] + part[0][3];
+    slots[blockIdx.x * 3 + 1] =
+        part[1][0] + part[1][1] + part[1][2] + part[1][3];
+    slots[blockIdx.x * 3 + 2] =
+        part[2][0] + part[2][1] + part[2][2] + part[2][3];
+    __threadfence();
+    const unsigned old = atomicAdd((unsigned*)ws, 1u);
+    s_last = (old == (unsigned)gridDim.x - 1u);
+    if (s_last) {
+      *(unsigned*)ws = 0u;  // reset the ticket for the next replay
+      __threadfence();
+    }
+  }
+  __syncthreads();
+  if (!s_last) return;
+  const int nb = (int)gridDim.x;
+  if (tid < nb * 3) s_fin[tid] = ((const volatile float*)slots)[tid];
+  __syncthreads();
+  if (tid == 0) {
+    float r0 = 0.f, r1 = 0.f, r2 = 0.f;
+    for (int b = 0; b < nb; ++b) {
+      r0 += s_fin[b * 3 + 0];
+      r1 += s_fin[b * 3 + 1];
+      r2 += s_fin[b * 3 + 2];
+    }
+    const float wfin = use_w ? r2 : 1.f;
+    const float denom = wfin * (float)B;
+    out[3] = r0; out[4] = r1; out[5] = r2;
+    out[0] = r0 / denom;
+    out[1] = r1 / denom;
+    out[2] = wfin;
+    out[6] = (r0 + r1) / denom;
+  }
+}
+
+// Priority write-back, three steps in stream order: the sampled leaves are
+// zeroed (k_critic_td_loss_per, or k_per_zero), k_per_max maxes the new
+// values in (non-negative floats order as their bit patterns, so an unsigned
+// atomicMax is exact and order-independent: a row drawn twice ends with the
+// larger value) and raises max_prio, k_per_resum re-sums the touched blocks.
+__global__ __launch_bounds__(256) void k_per_zero(
+    float* __restrict__ prio, const long long* __restrict__ idx, int B,
+    long n_prio) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= B) return;
+  const long flat = idx[i];
+  if (flat >= 0 && flat < n_prio) prio[flat] = 0.f;
+}
+
+__global__ __launch_bounds__(256) void k_per_max(
+    float* __restrict__ prio, float* __restrict__ maxp,
+    const long long* __restrict__ idx, const float* __restrict__ newp, int B,
+    long cap, long n_prio) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const long flat = i < B ? idx[i] : -1;
+  const bool ok = flat >= 0 && flat < n_prio;
+  float v = ok ? newp[i] : 0.f;
+  v = v > 0.f ? v : 0.f;            // a NaN must not win the bit-pattern max
+  if (ok) atomicMax((unsigned*)prio + flat, __float_as_uint(v));
+  // max_prio: B atomics on T words would serialise, so each wave first
+  // folds its rows shard by shard (a sampled batch is shard-major: one or
+  // two shards per wave) and issues one atomic per shard it holds
+  const int lane = threadIdx.x & 63;
+  int t = ok ? (int)(flat / cap) : -1;
+  unsigned long long todo = __ballot(ok);
+  while (todo != 0ull) {
+    const int cur = __shfl(t, __ffsll((long long)todo) - 1, 64);
+    float m = t == cur ? v : 0.f;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+      m = fmaxf(m, __shfl_xor(m, off, 64));
+    if (lane == 0) atomicMax((unsigned*)maxp + cur, __float_as_uint(m));
+    todo &= ~__ballot(t == cur);
+  }
+}
+
+// one wave per batch row, PER_RESUM_ROWS rows per workgroup (few workgroups:
+// the ticket is one atomic per workgroup on one word): re-sums the block the
+// row's leaf lies in (a block touched by several rows is re-summed by each,
+// to the same bits), then the last workgroup to finish recomputes every
+// shard's total.
+constexpr int PER_RESUM_ROWS = 16;
+
+__global__ __launch_bounds__(PER_RESUM_ROWS * 64) void k_per_resum(
+    const float* prio, float* bsum, float* total, const long long* idx,
+    unsigned* ticket, int B, int T, long cap, int nb, long n_prio) {
+  __shared__ int s_last;
+  const int lane = threadIdx.x & 63;
+  const int i = __builtin_amdgcn_readfirstlane(
+      (int)(blockIdx.x * PER_RESUM_ROWS + (threadIdx.x >> 6)));
+  if (i < B) {
+    long flat = idx[i];
+    flat = flat < 0 ? 0 : (flat >= n_prio ? n_prio - 1 : flat);
+    const long t = flat / cap;
+    const long b = (flat - t * cap) / PER_BLOCK;
+    const long base = b * PER_BLOCK;
+    const int n = (int)(cap - base < PER_BLOCK ? cap - base : PER_BLOCK);
+    const float v = per_wave_fixed_sum<false>(prio + t * cap + base, n, lane);
+    if (lane == 0) bsum[t * nb + b] = v;
+  }
+  per_finish_totals(bsum, total, ticket, nb, 0, T, &s_last);
+}
+
+// Ingest hook: rows written by ingest receive max_prio[t] of their shard.
+// grid = (nb, nt): block (b, y) owns leaf block b of shard t0 + y; if a
+// written range meets it, it stores max_prio[t] to the covered leaves and
+// re-sums the block from the values it holds.  Ranges: the descriptors of a
+// staged packed batch on the device (pk != nullptr: task d[0], rows d[3],
+// first row d[5], wrapping), or the one range (t0, r_start, r_rows).
+__device__ __forceinline__ bool per_in_range(long row, long start, long rows,
+                                             long cap) {
+  long d = row - start;
+  if (d < 0) d += cap;
+  return d < rows;
+}
+
+__global__ __launch_bounds__(256) void k_per_ingest(
+    const float* __restrict__ pk, int n_desc, int t_hdr, int t0, int r_start,
+    int r_rows, float* prio, float* bsum, float* total,
+    const float* __restrict__ maxp, unsigned* ticket, long cap, int nb) {
+  __shared__ float s[256];
+  __shared__ int s_last;
+  __shared__ int s_hit;
+  const int tid = threadIdx.x;
+  const int t = t0 + (int)blockIdx.y;
+  const long base = (long)blockIdx.x * PER_BLOCK;
+  const int n = (int)(cap - base < PER_BLOCK ? cap - base : PER_BLOCK);
+  const int* desc = pk != nullptr
+      ? reinterpret_cast<const int*>(pk) + PK_HDR + t_hdr : nullptr;
+  const int nd = pk != nullptr ? n_desc : 1;
+  if (tid == 0) s_hit = 0;
+  __syncthreads();
+  for (int k = tid; k < nd; k += 256) {
+    const int task = desc ? desc[k * PK_DESC] : t0;
+    const long rows = desc ? desc[k * PK_DESC + 3] : r_rows;
+    const long start = desc ? desc[k * PK_DESC + 5] : r_start;
+    if (task != t || rows < 1) continue;
+    // [start, start + rows) mod cap meets [base, base + n)?
+    const long end = start + rows;
+    const bool a = start < base + n && (end < cap ? end : cap) > base;
+    const bool w = end > cap && end - cap > base;
+    if (a || w) s_hit = 1;
+  }
+  __syncthreads();
+  if (s_hit) {
+    const float mp = maxp[t];
+    float acc = 0.f;
+    for (int k = tid; k < n; k += 256) {
+      const long row = base + k;
+      bool in = false;
+      for (int q = 0; q < nd && !in; ++q) {
+        const int task = desc ? desc[q * PK_DESC] : t0;
+        const long rows = desc ? desc[q * PK_DESC + 3] : r_rows;
+        const long start = desc ? desc[q * PK_DESC + 5] : r_start;
+        in = task == t && per_in_range(row, start, rows, cap);
+      }
+      float v;
+      if (in) {
+        prio[(long)t * cap + row] = mp;
+        v = mp;
+      } else {
+        v = prio[(long)t * cap + row];
+      }
+      acc += v;
+    }
+    const float v = per_fold256(acc, s);
+    if (tid == 0) bsum[(long)t * nb + blockIdx.x] = v;
+  }
+  per_finish_totals(bsum, total, ticket, nb, t0, (int)gridDim.y, &s_last);
+}
+
 // K6 actor/alpha forward + backward in one launch (k_actor_alpha_loss_fwd_mb
 // + the workspace path of k_actor_alpha_loss_bwd2).  ws = ticket, 32*4
 // metric slots, then gridDim*T alpha-gradient slots; ONE ticket serves both
@@ -2631,6 +3099,269 @@ static void polyak_(torch::Tensor t, torch::Tensor s, double tau,
                      n, (float)tau, mp);
 }
 
+// -- prioritized replay ------------------------------------------------------
+// Shared validation of the priority state: prio [T, cap], bsum [T, nb] with
+// nb = ceil(cap / PER_BLOCK), total [T], maxp [T]; ws holds the two tickets.
+static void per_check_state(const torch::Tensor& prio,
+                            const torch::Tensor& bsum,
+                            const torch::Tensor& total, long T, long cap) {
+  CHECK_IN(prio); CHECK_IN(bsum); CHECK_IN(total);
+  const long nb = (cap + PER_BLOCK - 1) / PER_BLOCK;
+  TORCH_CHECK(T >= 1 && cap >= 1 && cap <= (1L << 24),
+              "prioritized replay: geometry out of range");
+  TORCH_CHECK(prio.is_contiguous() && prio.numel() == T * cap,
+              "priorities must be a contiguous [T, cap] tensor");
+  TORCH_CHECK(bsum.is_contiguous() && bsum.numel() == T * nb,
+              "block sums must be a contiguous [T, ceil(cap / PER_BLOCK)] "
+              "tensor");
+  TORCH_CHECK(total.is_contiguous() && total.numel() == T,
+              "totals must hold one entry per task");
+}
+
+static void per_check_ws(const torch::Tensor& ws) {
+  TORCH_CHECK(ws.is_cuda() && ws.scalar_type() == torch::kInt32
+              && ws.is_contiguous() && ws.numel() >= 2,
+              "prioritized replay workspace must be an int32 HIP tensor of "
+              "at least 2 words");
+}
+
+// Proportional draw + gather (k_replay_sample_per).  idx_out receives the B
+// flat row indices (t * cap + row), w_out the raw IS weights.
+static std::vector<torch::Tensor> replay_sample_per(
+    torch::Tensor states, torch::Tensor actions, torch::Tensor rewards,
+    torch::Tensor next_states, torch::Tensor dones, torch::Tensor sizes,
+    torch::Tensor prio, torch::Tensor bsum, torch::Tensor total,
+    torch::Tensor beta, long B, torch::Tensor rng, torch::Tensor idx_out,
+    torch::Tensor w_out) {
+  CHECK_IN(states); CHECK_IN(actions); CHECK_IN(rewards);
+  CHECK_IN(next_states); CHECK_IN(dones); CHECK_IN(sizes); CHECK_IN(beta);
+  CHECK_IN(w_out);
+  TORCH_CHECK(rng.is_cuda() && rng.scalar_type() == torch::kInt64
+              && rng.numel() >= 1, "rng counter must be an int64 HIP tensor");
+  TORCH_CHECK(states.dim() == 3 && states.is_contiguous(),
+              "states must be a contiguous [T, cap, Ds] tensor");
+  const long T = states.size(0), cap = states.size(1);
+  const long Ds = states.size(2);
+  per_check_state(prio, bsum, total, T, cap);
+  TORCH_CHECK(actions.dim() == 3 && actions.is_contiguous()
+              && actions.size(0) == T && actions.size(1) == cap,
+              "actions must be a contiguous [T, cap, Da] tensor");
+  const long Da = actions.size(2);
+  TORCH_CHECK(next_states.is_contiguous()
+              && next_states.sizes() == states.sizes(),
+              "next_states must match states");
+  TORCH_CHECK(rewards.is_contiguous() && rewards.numel() == T * cap
+              && dones.is_contiguous() && dones.numel() == T * cap,
+              "rewards/dones must be contiguous [T, cap, 1] tensors");
+  TORCH_CHECK(sizes.is_contiguous() && sizes.numel() == T,
+              "sizes must hold one entry per task");
+  TORCH_CHECK(beta.numel() >= 1, "beta must hold one element");
+  TORCH_CHECK(B >= 1 && B <= 8192 && B % T == 0,
+              "batch must be in [1, 8192] and divide by num_tasks");
+  TORCH_CHECK(idx_out.is_cuda() && idx_out.scalar_type() == torch::kInt64
+              && idx_out.is_contiguous() && idx_out.numel() == B,
+              "idx_out must be a contiguous int64 HIP tensor of B entries");
+  TORCH_CHECK(w_out.is_contiguous() && w_out.numel() == B,
+              "w_out must be a contiguous fp32 tensor of B entries");
+  const int per = (int)(B / T);
+  const long nb = (cap + PER_BLOCK - 1) / PER_BLOCK;
+  auto opt = states.options();
+  auto o_s = torch::empty({B, Ds}, opt);
+  auto o_a = torch::empty({B, Da}, opt);
+  auto o_r = torch::empty({B, 1}, opt);
+  auto o_ns = torch::empty({B, Ds}, opt);
+  auto o_d = torch::empty({B, 1}, opt);
+  hipLaunchKernelGGL(k_replay_sample_per, dim3((B + 3) / 4), dim3(256), 0,
+                     cur_stream(), states.data_ptr<float>(),
+                     actions.data_ptr<float>(), rewards.data_ptr<float>(),
+                     next_states.data_ptr<float>(), dones.data_ptr<float>(),
+                     sizes.data_ptr<float>(), prio.data_ptr<float>(),
+                     bsum.data_ptr<float>(), total.data_ptr<float>(),
+                     beta.data_ptr<float>(),
+                     (const long long*)rng.data_ptr<long>(),
+                     o_s.data_ptr<float>(), o_a.data_ptr<float>(),
+                     o_r.data_ptr<float>(), o_ns.data_ptr<float>(),
+                     o_d.data_ptr<float>(),
+                     (long long*)idx_out.data_ptr<long>(),
+                     w_out.data_ptr<float>(), (int)B, (int)T, per, cap,
+                     (int)nb, (int)Ds, (int)Da);
+  return {o_s, o_a, o_r, o_ns, o_d};
+}
+
+// critic_td_loss with IS weights `isw` (raw, [B]).  Returns {closs[8],
+// dq[2,B,1] bf16, new_prio[B]}.  Given `prio` (the [T, cap] leaves) and `idx`
+// (the rows' flat indices, int64 [B]) it also zeroes the sampled leaves, the
+// first step of the write-back (per_update with zeroed = true follows).
+static std::vector<torch::Tensor> critic_td_loss_per(
+    torch::Tensor r, torch::Tensor d, torch::Tensor q1t, torch::Tensor q2t,
+    torch::Tensor nlp, torch::Tensor q1, torch::Tensor q2,
+    torch::Tensor states, torch::Tensor log_alpha, long T, long use_w,
+    double gamma, double rs, torch::Tensor ws, torch::Tensor isw,
+    double per_alpha, double per_eps,
+    c10::optional<torch::Tensor> prio = c10::nullopt,
+    c10::optional<torch::Tensor> idx = c10::nullopt) {
+  CHECK_IN(r); CHECK_IN(d); CHECK_IN(q1t); CHECK_IN(q2t); CHECK_IN(nlp);
+  CHECK_IN(q1); CHECK_IN(q2); CHECK_IN(states); CHECK_IN(log_alpha);
+  CHECK_IN(ws); CHECK_IN(isw);
+  const long B = q1.size(0);
+  const long nblk = (B + 255) / 256;
+  TORCH_CHECK(B >= 1 && nblk <= 32, "critic_td_loss_per: 1 <= B <= 8192");
+  TORCH_CHECK(T >= 1 && T <= 32 && log_alpha.numel() >= T, "T <= 32");
+  TORCH_CHECK(ws.numel() >= 1 + 32 * 3, "workspace too small");
+  TORCH_CHECK(states.dim() == 2 && states.is_contiguous()
+              && states.size(0) == B && states.size(1) >= T);
+  TORCH_CHECK(isw.is_contiguous() && isw.numel() == B,
+              "IS weights must be a contiguous fp32 tensor of B entries");
+  TORCH_CHECK(per_alpha >= 0.0 && per_eps >= 0.0,
+              "per_alpha and per_eps must not be negative");
+  TORCH_CHECK(prio.has_value() == idx.has_value(),
+              "give both prio and idx, or neither");
+  float* prio_p = nullptr;
+  const long long* idx_p = nullptr;
+  long n_prio = 0;
+  if (prio.has_value()) {
+    CHECK_IN(*prio);
+    TORCH_CHECK(prio->is_contiguous(), "priorities must be contiguous");
+    TORCH_CHECK(idx->is_cuda() && idx->scalar_type() == torch::kInt64
+                && idx->is_contiguous() && idx->numel() == B,
+                "idx must be a contiguous int64 HIP tensor of B entries");
+    prio_p = prio->data_ptr<float>();
+    idx_p = (const long long*)idx->data_ptr<long>();
+    n_prio = prio->numel();
+  }
+  auto rc = r.contiguous(); auto dc = d.contiguous();
+  auto q1tc = q1t.contiguous(); auto q2tc = q2t.contiguous();
+  auto lpc = nlp.contiguous();
+  auto q1c = q1.contiguous(); auto q2c = q2.contiguous();
+  TORCH_CHECK(rc.numel() == B && dc.numel() == B && q1tc.numel() == B
+              && q2tc.numel() == B && lpc.numel() == B && q1c.numel() == B
+              && q2c.numel() == B, "critic_td_loss_per: B elements per input");
+  const long oh_stride = states.size(1);
+  const float* oh = states.data_ptr<float>() + (oh_stride - T);
+  auto out = torch::empty({8}, q1.options());
+  auto dq = torch::empty({2, B, 1}, q1.options().dtype(torch::kBFloat16));
+  auto newp = torch::empty({B}, q1.options());
+  hipLaunchKernelGGL(k_critic_td_loss_per, dim3(nblk), dim3(256), 0,
+                     cur_stream(), rc.data_ptr<float>(),
+                     dc.data_ptr<float>(), q1tc.data_ptr<float>(),
+                     q2tc.data_ptr<float>(), lpc.data_ptr<float>(),
+                     q1c.data_ptr<float>(), q2c.data_ptr<float>(), oh,
+                     log_alpha.data_ptr<float>(), out.data_ptr<float>(),
+                     ws.data_ptr<float>(), (unsigned short*)dq.data_ptr(),
+                     (int)B, (int)T, (int)oh_stride, (int)use_w,
+                     (float)gamma, (float)rs, isw.data_ptr<float>(),
+                     newp.data_ptr<float>(), prio_p, idx_p, n_prio,
+                     (float)per_alpha, (float)per_eps);
+  return {out, dq, newp};
+}
+
+// Priority write-back: leaves[idx] = max over duplicates of newp, max_prio
+// raised, touched blocks and all totals re-summed.  zeroed: the sampled
+// leaves were already zeroed (critic_td_loss_per did it).
+static void per_update(torch::Tensor prio, torch::Tensor bsum,
+                       torch::Tensor total, torch::Tensor maxp,
+                       torch::Tensor idx, torch::Tensor newp,
+                       torch::Tensor ws, bool zeroed) {
+  TORCH_CHECK(prio.dim() == 2, "priorities must be [T, cap]");
+  const long T = prio.size(0), cap = prio.size(1);
+  per_check_state(prio, bsum, total, T, cap);
+  per_check_ws(ws);
+  CHECK_IN(maxp); CHECK_IN(newp);
+  TORCH_CHECK(maxp.is_contiguous() && maxp.numel() == T,
+              "max_prio must hold one entry per task");
+  const long B = idx.numel();
+  TORCH_CHECK(idx.is_cuda() && idx.scalar_type() == torch::kInt64
+              && idx.is_contiguous(),
+              "indices must be a contiguous int64 HIP tensor");
+  TORCH_CHECK(newp.is_contiguous() && newp.numel() == B,
+              "one new priority per index");
+  TORCH_CHECK(B <= 8192, "per_update: at most 8192 rows");
+  if (B == 0) return;
+  const long nb = (cap + PER_BLOCK - 1) / PER_BLOCK;
+  const long long* ip = (const long long*)idx.data_ptr<long>();
+  auto st = cur_stream();
+  if (!zeroed)
+    hipLaunchKernelGGL(k_per_zero, dim3((B + 255) / 256), dim3(256), 0, st,
+                       prio.data_ptr<float>(), ip, (int)B, T * cap);
+  hipLaunchKernelGGL(k_per_max, dim3((B + 255) / 256), dim3(256), 0, st,
+                     prio.data_ptr<float>(), maxp.data_ptr<float>(), ip,
+                     newp.data_ptr<float>(), (int)B, cap, T * cap);
+  hipLaunchKernelGGL(k_per_resum,
+                     dim3((B + PER_RESUM_ROWS - 1) / PER_RESUM_ROWS),
+                     dim3(PER_RESUM_ROWS * 64), 0, st,
+                     prio.data_ptr<float>(), bsum.data_ptr<float>(),
+                     total.data_ptr<float>(), ip,
+                     (unsigned*)ws.data_ptr<int>(), (int)B, (int)T, cap,
+                     (int)nb, T * cap);
+}
+
+// Ingest hook, one shard: rows [start, start + rows) mod cap of shard t
+// receive max_prio[t].
+static void per_ingest_range(torch::Tensor prio, torch::Tensor bsum,
+                             torch::Tensor total, torch::Tensor maxp,
+                             torch::Tensor ws, long t, long start,
+                             long rows) {
+  TORCH_CHECK(prio.dim() == 2, "priorities must be [T, cap]");
+  const long T = prio.size(0), cap = prio.size(1);
+  per_check_state(prio, bsum, total, T, cap);
+  per_check_ws(ws);
+  CHECK_IN(maxp);
+  TORCH_CHECK(maxp.is_contiguous() && maxp.numel() == T,
+              "max_prio must hold one entry per task");
+  TORCH_CHECK(t >= 0 && t < T && start >= 0 && start < cap && rows >= 0
+              && rows <= cap, "per_ingest_range: range outside the shard");
+  if (rows == 0) return;
+  const long nb = (cap + PER_BLOCK - 1) / PER_BLOCK;
+  hipLaunchKernelGGL(k_per_ingest, dim3(nb, 1), dim3(256), 0, cur_stream(),
+                     (const float*)nullptr, 0, 0, (int)t, (int)start,
+                     (int)rows, prio.data_ptr<float>(),
+                     bsum.data_ptr<float>(), total.data_ptr<float>(),
+                     maxp.data_ptr<float>(),
+                     (unsigned*)ws.data_ptr<int>() + 1, cap, (int)nb);
+}
+
+// Ingest hook of the packed path: one launch per batch, reading the
+// descriptors of the staged batch on the device.  `header` is the host copy
+// (checked here, as replay_ingest does).
+static void per_ingest_packed(torch::Tensor staging, torch::Tensor header,
+                              torch::Tensor prio, torch::Tensor bsum,
+                              torch::Tensor total, torch::Tensor maxp,
+                              torch::Tensor ws) {
+  CHECK_IN(staging);
+  TORCH_CHECK(prio.dim() == 2, "priorities must be [T, cap]");
+  const long T = prio.size(0), cap = prio.size(1);
+  per_check_state(prio, bsum, total, T, cap);
+  per_check_ws(ws);
+  CHECK_IN(maxp);
+  TORCH_CHECK(maxp.is_contiguous() && maxp.numel() == T,
+              "max_prio must hold one entry per task");
+  TORCH_CHECK(header.device().is_cpu() &&
+                  header.scalar_type() == torch::kFloat32 &&
+                  header.is_contiguous() && staging.is_contiguous(),
+              "header must be a contiguous fp32 host tensor");
+  const long hn = header.numel();
+  TORCH_CHECK(hn >= PK_HDR + T, "packed header truncated");
+  const int32_t* h = reinterpret_cast<const int32_t*>(
+      header.data_ptr<float>());
+  const long n_desc = h[0];
+  TORCH_CHECK(h[1] == T, "packed batch built for another task count");
+  TORCH_CHECK(n_desc >= 1 && PK_HDR + T + n_desc * PK_DESC <= hn
+              && PK_HDR + T + n_desc * PK_DESC <= staging.numel(),
+              "packed descriptor count out of range");
+  for (long k = 0; k < n_desc; ++k) {
+    const int32_t* d = h + PK_HDR + T + k * PK_DESC;
+    TORCH_CHECK(d[0] >= 0 && d[0] < T && d[3] >= 1 && d[3] <= cap
+                && d[5] >= 0 && d[5] < cap,
+                "packed descriptor out of range");
+  }
+  const long nb = (cap + PER_BLOCK - 1) / PER_BLOCK;
+  hipLaunchKernelGGL(k_per_ingest, dim3(nb, T), dim3(256), 0, cur_stream(),
+                     staging.data_ptr<float>(), (int)n_desc, (int)T, 0, 0, 0,
+                     prio.data_ptr<float>(), bsum.data_ptr<float>(),
+                     total.data_ptr<float>(), maxp.data_ptr<float>(),
+                     (unsigned*)ws.data_ptr<int>() + 1, cap, (int)nb);
+}
+
 void register_shm_ring(pybind11::module_& m);
 void register_bf16(pybind11::module_& m);
 void register_chain(pybind11::module_& m);
@@ -2663,6 +3394,38 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           pybind11::arg("states"), pybind11::arg("actions"),
           pybind11::arg("rewards"), pybind11::arg("next_states"),
           pybind11::arg("dones"), pybind11::arg("sizes"));
+  mod.def("replay_sample_per", &replay_sample_per,
+          "stratified proportional (prioritized) replay gather",
+          pybind11::arg("states"), pybind11::arg("actions"),
+          pybind11::arg("rewards"), pybind11::arg("next_states"),
+          pybind11::arg("dones"), pybind11::arg("sizes"),
+          pybind11::arg("prio"), pybind11::arg("bsum"),
+          pybind11::arg("total"), pybind11::arg("beta"), pybind11::arg("B"),
+          pybind11::arg("rng"), pybind11::arg("idx_out"),
+          pybind11::arg("w_out"));
+  mod.def("critic_td_loss_per", &critic_td_loss_per,
+          pybind11::arg("r"), pybind11::arg("d"), pybind11::arg("q1t"),
+          pybind11::arg("q2t"), pybind11::arg("nlp"), pybind11::arg("q1"),
+          pybind11::arg("q2"), pybind11::arg("states"),
+          pybind11::arg("log_alpha"), pybind11::arg("T"),
+          pybind11::arg("use_w"), pybind11::arg("gamma"),
+          pybind11::arg("rs"), pybind11::arg("ws"), pybind11::arg("isw"),
+          pybind11::arg("per_alpha"), pybind11::arg("per_eps"),
+          pybind11::arg("prio") = pybind11::none(),
+          pybind11::arg("idx") = pybind11::none());
+  mod.def("per_update", &per_update, "prioritized replay write-back",
+          pybind11::arg("prio"), pybind11::arg("bsum"),
+          pybind11::arg("total"), pybind11::arg("maxp"), pybind11::arg("idx"),
+          pybind11::arg("newp"), pybind11::arg("ws"),
+          pybind11::arg("zeroed") = false);
+  mod.def("per_ingest_range", &per_ingest_range,
+          pybind11::arg("prio"), pybind11::arg("bsum"),
+          pybind11::arg("total"), pybind11::arg("maxp"), pybind11::arg("ws"),
+          pybind11::arg("t"), pybind11::arg("start"), pybind11::arg("rows"));
+  mod.def("per_ingest_packed", &per_ingest_packed,
+          pybind11::arg("staging"), pybind11::arg("header"),
+          pybind11::arg("prio"), pybind11::arg("bsum"),
+          pybind11::arg("total"), pybind11::arg("maxp"), pybind11::arg("ws"));
   mod.def("squashed_gaussian_fwd", &squashed_gaussian_fwd,
           pybind11::arg("mu"), pybind11::arg("lsr"),
           pybind11::arg("eps"), pybind11::arg("k"),

@@ -329,3 +329,201 @@ def replay_sample_indices_norepl(sizes, B: int, T: int, ctr) -> torch.Tensor:
     j = torch.arange(per, device=dev, dtype=torch.int64)
     return norepl_index(n[:, None], t[:, None], j[None, :],
                         c[None, :]).reshape(-1)
+
+
+# ---------------------------------------------------------------------------
+# Prioritized replay (docs/KERNELS.md "Prioritized replay"): the CPU path and
+# the exact oracle of k_replay_sample_per, k_critic_td_loss_per's priorities,
+# the write-back kernels and the ingest hook.  State of a replay with T
+# shards of ``cap`` rows: leaves ``prio [T, cap]`` (0 = never written), block
+# sums ``bsum [T, ceil(cap / PER_BLOCK)]``, ``total [T]``, ``max_prio [T]``.
+# Sums are only ever recomputed from what they cover, in one fixed order.
+# ---------------------------------------------------------------------------
+
+PER_BLOCK = 1024     # leaves per block sum
+
+
+def per_fixed_sum(v: torch.Tensor) -> torch.Tensor:
+    """Sum over the last dim in the kernels' fixed order: 256 strided
+    partials (element i, i + 256, i + 512, ... added in that order), folded
+    by halves (i with i + 128, then + 64, ... + 1)."""
+    n = v.shape[-1]
+    v = F.pad(v, (0, (-n) % 256)).reshape(*v.shape[:-1], -1, 256)
+    acc = v[..., 0, :]
+    for k in range(1, v.shape[-2]):
+        acc = acc + v[..., k, :]
+    h = 128
+    while h >= 1:
+        acc = acc[..., :h] + acc[..., h:2 * h]
+        h //= 2
+    return acc[..., 0]
+
+
+def per_resum(prio: torch.Tensor):
+    """``(bsum, total)`` of leaves ``prio [T, cap]`` — the invariant every
+    prioritized-replay kernel maintains, bit for bit."""
+    T, cap = prio.shape
+    nb = (cap + PER_BLOCK - 1) // PER_BLOCK
+    leaves = F.pad(prio, (0, nb * PER_BLOCK - cap)).reshape(T, nb, PER_BLOCK)
+    bsum = per_fixed_sum(leaves)
+    return bsum, per_fixed_sum(bsum)
+
+
+def _hs_scan64(v: torch.Tensor) -> torch.Tensor:
+    """Hillis-Steele inclusive scan over a last dim of 64 (the wave scan of
+    the kernel: element l adds element l - off for off = 1, 2, ... 32)."""
+    for off in (1, 2, 4, 8, 16, 32):
+        v = torch.cat([v[..., :off], v[..., off:] + v[..., :-off]], dim=-1)
+    return v
+
+
+def _per_prefix(p: torch.Tensor) -> torch.Tensor:
+    """Inclusive prefix sums over the last dim as the kernel forms them:
+    chunks of 64, a wave scan each, plus the running base."""
+    n = p.shape[-1]
+    c = F.pad(p, (0, (-n) % 64)).reshape(*p.shape[:-1], -1, 64)
+    sc = _hs_scan64(c)
+    base = torch.zeros(p.shape[:-1], dtype=p.dtype, device=p.device)
+    out = []
+    for k in range(sc.shape[-2]):
+        incl = base[..., None] + sc[..., k, :]
+        out.append(incl)
+        base = incl[..., 63]
+    return torch.cat(out, dim=-1)[..., :n]
+
+
+def _per_search(p: torch.Tensor, x: torch.Tensor):
+    """Per row of ``p [R, n]``: the first k with ``p[k] > 0`` whose inclusive
+    prefix exceeds ``x [R]`` and the prefix before it; where there is none
+    (rounding), the last k with ``p[k] > 0`` (0 if none).  Returns
+    ``(k, excl, found)``."""
+    n = p.shape[-1]
+    incl = _per_prefix(p)
+    ar = torch.arange(n, device=p.device).expand_as(p)
+    hit = (incl > x[:, None]) & (p > 0)
+    found = hit.any(dim=-1)
+    first = torch.where(hit, ar, torch.full_like(ar, n)).min(dim=-1).values
+    last = torch.where(p > 0, ar, torch.full_like(ar, -1)).max(dim=-1).values
+    k = torch.where(found, first, last.clamp(min=0))
+    prev = incl.gather(1, (k - 1).clamp(min=0)[:, None])[:, 0]
+    excl = torch.where(k > 0, prev, torch.zeros_like(prev))
+    return k, excl, found
+
+
+def per_uniforms(B: int, ctr) -> torch.Tensor:
+    """The (0, 1) uniform k_replay_sample derives from the rng counter for
+    each of the B batch rows (fp32)."""
+    if not torch.is_tensor(ctr):
+        ctr = torch.tensor(_i64(int(ctr)), dtype=torch.int64)
+    c = ctr.reshape(-1)[:1].to(device="cpu", dtype=torch.int64)
+    i = torch.arange(B, dtype=torch.int64)
+    h = _sm64(c * 0x100000001 + i * 2 + 2)
+    u = (_lsr(h, 40) + 1).to(torch.float32) * 5.9604644775390625e-8
+    return torch.where(u < 1.0, u, torch.full_like(u, 0.99999994))
+
+
+@torch.no_grad()
+def per_sample_indices(prio: torch.Tensor, bsum: torch.Tensor,
+                       total: torch.Tensor, sizes, B: int, T: int, ctr,
+                       return_x: bool = False):
+    """In-shard indices of one stratified proportional draw: int64
+    ``[T * (B // T)]``, rows ``t * per .. (t + 1) * per - 1`` from shard t.
+    Row j of a shard draws at ``x = (float(j) + u) * (total_t / float(per))``
+    (fp32, in that order; ``u`` from :func:`per_uniforms`) and takes the
+    first row whose inclusive prefix sum of the priorities exceeds x — first
+    the block, over ``bsum``, then the leaf, over the block's leaves and x
+    minus the prefix before the block.  Rounding: if no block (leaf)
+    qualifies, the last one with a non-zero sum (priority) is taken; a row
+    with zero priority is never taken.  An empty shard yields 0."""
+    dev = prio.device
+    per = int(B) // int(T)
+    cap = prio.shape[1]
+    nb = bsum.shape[1]
+    sizes = torch.as_tensor(sizes, dtype=torch.float32, device=dev) \
+        .reshape(-1)[:T].clamp(max=float(cap))
+    u = per_uniforms(per * T, ctr).to(dev).reshape(T, per)
+    j = torch.arange(per, dtype=torch.float32, device=dev)
+    tot = total.reshape(-1)[:T].to(torch.float32)
+    x = (j[None, :] + u) * (tot / float(per))[:, None]
+    leaves = F.pad(prio, (0, nb * PER_BLOCK - cap)).reshape(T, nb, PER_BLOCK)
+    idx = torch.zeros(T, per, dtype=torch.int64, device=dev)
+    for t in range(T):
+        if not (float(sizes[t]) >= 1.0 and float(tot[t]) > 0.0):
+            continue
+        b, excl, found = _per_search(bsum[t].expand(per, nb), x[t])
+        xr = torch.where(found, x[t] - excl,
+                         torch.full_like(excl, float("inf")))
+        k, _, _ = _per_search(leaves[t][b], xr)
+        idx[t] = b * PER_BLOCK + k
+    idx = idx.reshape(-1)
+    return (idx, x.reshape(-1)) if return_x else idx
+
+
+@torch.no_grad()
+def per_is_weights(prio: torch.Tensor, total: torch.Tensor, sizes,
+                   idx: torch.Tensor, beta) -> torch.Tensor:
+    """Raw importance-sampling weights ``(n_t * p_i / total_t) ** -beta`` of
+    the in-shard indices ``idx [T * per]`` (shard-major); 1 for an empty
+    shard or a zero priority."""
+    T, cap = prio.shape
+    dev = prio.device
+    per = idx.numel() // T
+    n = torch.as_tensor(sizes, dtype=torch.float32, device=dev) \
+        .reshape(-1)[:T].clamp(max=float(cap))
+    beta = torch.as_tensor(beta, dtype=torch.float32, device=dev).reshape(-1)[0]
+    p = prio.gather(1, idx.reshape(T, per))
+    tot = total.reshape(-1)[:T, None]
+    ok = (n[:, None] >= 1.0) & (tot > 0.0) & (p > 0.0)
+    ratio = torch.where(ok, n[:, None] * p / tot, torch.ones_like(p))
+    return torch.pow(ratio, -beta).reshape(-1)
+
+
+def per_new_priorities(d1: torch.Tensor, d2: torch.Tensor, alpha: float,
+                       eps: float) -> torch.Tensor:
+    """``(0.5 (|d1| + |d2|) + eps) ** alpha`` of the two TD errors."""
+    return torch.pow(0.5 * (d1.abs() + d2.abs()) + eps, alpha).reshape(-1)
+
+
+def _per_resum_blocks(prio, bsum, total, t: int, rows: torch.Tensor) -> None:
+    """Re-sum the blocks of shard t holding ``rows`` and the shard total."""
+    cap = prio.shape[1]
+    for b in torch.unique(rows // PER_BLOCK).tolist():
+        leaf = prio[t, b * PER_BLOCK:min(cap, (b + 1) * PER_BLOCK)]
+        bsum[t, b] = per_fixed_sum(leaf)
+    total[t] = per_fixed_sum(bsum[t])
+
+
+@torch.no_grad()
+def per_update_(prio: torch.Tensor, bsum: torch.Tensor, total: torch.Tensor,
+                max_prio: torch.Tensor, idx: torch.Tensor,
+                new_prio: torch.Tensor) -> None:
+    """Write-back: every row of the flat indices ``idx`` (``t * cap + row``)
+    takes its new priority, a row listed more than once the MAXIMUM of its
+    values; ``max_prio[t]`` is raised to the largest value written; touched
+    blocks and the totals are re-summed.  A value that is not positive
+    (NaN included) counts as 0."""
+    T, cap = prio.shape
+    idx = idx.reshape(-1).to(torch.int64)
+    v = new_prio.reshape(-1).to(torch.float32)
+    v = torch.where(v > 0, v, torch.zeros_like(v))
+    flat = prio.reshape(-1)
+    flat[idx] = 0.0
+    flat.scatter_reduce_(0, idx, v, reduce="amax", include_self=True)
+    t_of = idx // cap
+    max_prio.scatter_reduce_(0, t_of, v, reduce="amax", include_self=True)
+    for t in torch.unique(t_of).tolist():
+        _per_resum_blocks(prio, bsum, total, t, idx[t_of == t] - t * cap)
+
+
+@torch.no_grad()
+def per_ingest_(prio: torch.Tensor, bsum: torch.Tensor, total: torch.Tensor,
+                max_prio: torch.Tensor, t: int, start: int, rows: int) -> None:
+    """Ingest hook: rows ``[start, start + rows) mod cap`` of shard t receive
+    ``max_prio[t]``; touched blocks and the shard total are re-summed."""
+    cap = prio.shape[1]
+    if rows <= 0:
+        return
+    r = (torch.arange(min(int(rows), cap), device=prio.device)
+         + int(start)) % cap
+    prio[t, r] = max_prio[t]
+    _per_resum_blocks(prio, bsum, total, t, r)

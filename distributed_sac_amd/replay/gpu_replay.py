@@ -30,6 +30,12 @@ semantics: each shard's rows of one batch are distinct, drawn by a keyed
 permutation evaluated per row (``k_replay_sample_norepl`` /
 ``torch_ref.replay_sample_indices_norepl``) — inside the captured update,
 with no host round trip and no 1e6-element randperm.
+
+``sampling="prioritized"`` (net-new; the reference has none) is proportional
+prioritized experience replay with importance-sampling weights: priorities
+live next to the rings as a flat two-level sum, the draw, the weights and the
+priority write-back all run inside the captured update (docs/KERNELS.md
+"Prioritized replay").
 """
 
 from __future__ import annotations
@@ -41,7 +47,39 @@ import numpy as np
 import torch
 
 FIELDS = ("states", "actions", "rewards", "next_states", "dones")
-SAMPLING_MODES = ("replace", "without_replacement")
+SAMPLING_MODES = ("replace", "without_replacement", "prioritized")
+PER_DEFAULTS = {"per_alpha": 0.6, "per_beta": 0.4,
+                "per_beta_anneal_steps": 0, "per_eps": 1e-6}
+
+
+def check_per_params(per_alpha=None, per_beta=None,
+                     per_beta_anneal_steps=None, per_eps=None) -> dict:
+    """The four prioritized-replay settings with defaults filled in;
+    ``ValueError`` for a value outside its range."""
+    out = dict(PER_DEFAULTS)
+    given = {"per_alpha": per_alpha, "per_beta": per_beta,
+             "per_beta_anneal_steps": per_beta_anneal_steps,
+             "per_eps": per_eps}
+    for k, v in given.items():
+        if v is None:
+            continue
+        try:
+            out[k] = int(v) if k == "per_beta_anneal_steps" else float(v)
+            exact = out[k] == v
+        except (TypeError, ValueError):
+            exact = False
+        if not exact or isinstance(v, bool):
+            raise ValueError(f"{k} must be a number, got {v!r}")
+    if not 0.0 <= out["per_alpha"] < float("inf"):
+        raise ValueError(f"per_alpha must be >= 0, got {per_alpha!r}")
+    if not 0.0 <= out["per_beta"] <= 1.0:
+        raise ValueError(f"per_beta must be in [0, 1], got {per_beta!r}")
+    if out["per_beta_anneal_steps"] < 0:
+        raise ValueError("per_beta_anneal_steps must be >= 0, got "
+                         f"{per_beta_anneal_steps!r}")
+    if not 0.0 < out["per_eps"] < float("inf"):
+        raise ValueError(f"per_eps must be > 0, got {per_eps!r}")
+    return out
 
 
 class ReplayShard:
@@ -75,6 +113,8 @@ class ReplayShard:
         # append OUTSIDE any captured region; read inside the graph)
         self.size_dev = (size_dev if size_dev is not None
                          else torch.zeros(1, device=dev))
+        # prioritized replay: called with (first row, rows) after a write
+        self.on_append = None
 
     def __len__(self) -> int:
         return self.size
@@ -106,6 +146,8 @@ class ReplayShard:
             if head < n:   # wrap: the tail goes to the front
                 dst[: n - head].copy_(src[head:], non_blocking=True)
         self.write_ptr = (wp + n) % self.capacity
+        if self.on_append is not None:
+            self.on_append(wp, n)
         new_size = min(self.size + n, self.capacity)
         if new_size != self.size:   # no kernel once the shard is full
             self.size = new_size
@@ -182,16 +224,28 @@ class ShardedReplay:
     def __init__(self, buffer_size: int, num_tasks: int, state_dim: int,
                  action_dim: int, device: torch.device | str = "cpu",
                  seed: Optional[int] = None,
-                 sampling: Optional[str] = None):
+                 sampling: Optional[str] = None,
+                 per_alpha: Optional[float] = None,
+                 per_beta: Optional[float] = None,
+                 per_beta_anneal_steps: Optional[int] = None,
+                 per_eps: Optional[float] = None):
         # "replace" (default): independent uniform draws per row;
         # "without_replacement": each shard's rows of a batch are distinct
-        # (the reference's random.sample), drawn by a keyed permutation
+        # (the reference's random.sample), drawn by a keyed permutation;
+        # "prioritized": proportional to per-row priorities, with
+        # importance-sampling weights (the per_* settings)
         if sampling is None:
             sampling = os.environ.get("DSAC_SAMPLING", "replace")
         if sampling not in SAMPLING_MODES:
-            raise ValueError(f"sampling must be 'replace' or "
-                             f"'without_replacement', got {sampling!r}")
+            raise ValueError(f"sampling must be 'replace', "
+                             f"'without_replacement' or 'prioritized', "
+                             f"got {sampling!r}")
         self.sampling = sampling
+        per = check_per_params(per_alpha, per_beta, per_beta_anneal_steps,
+                               per_eps)
+        self.per_alpha, self.per_eps = per["per_alpha"], per["per_eps"]
+        self.per_beta0 = per["per_beta"]
+        self.per_beta_anneal_steps = per["per_beta_anneal_steps"]
         self.num_tasks = num_tasks
         self.device = torch.device(device)
         per_task = int(buffer_size) // num_tasks  # reference replay_buffers.py:37-41
@@ -213,6 +267,25 @@ class ShardedReplay:
                                  self.f_dones[t]),
                         size_dev=self.sizes_dev[t:t + 1])
             for t in range(num_tasks)]
+        # prioritized replay state (this mode only): leaves, block sums
+        # over PER_BLOCK leaves, per-shard total and running maximum, beta
+        self.per_prio = self.per_bsum = self.per_total = None
+        self.per_max = self.per_beta = self._per_ws = None
+        if sampling == "prioritized":
+            from ..ops import torch_ref
+            if per_task < 1 or per_task > (1 << 24):
+                raise ValueError("prioritized replay: shard capacity must be "
+                                 "in [1, 2^24]")
+            nb = (per_task + torch_ref.PER_BLOCK - 1) // torch_ref.PER_BLOCK
+            self.per_prio = torch.zeros(num_tasks, per_task, device=dev)
+            self.per_bsum = torch.zeros(num_tasks, nb, device=dev)
+            self.per_total = torch.zeros(num_tasks, device=dev)
+            self.per_max = torch.ones(num_tasks, device=dev)
+            self.per_beta = torch.full((1,), self.per_beta0, device=dev)
+            self._per_ws = torch.zeros(2, dtype=torch.int32, device=dev)
+            for t, shard in enumerate(self.shards):
+                shard.on_append = (
+                    lambda start, n, t=t: self._per_ingest(t, start, n))
         self.generator = None
         if seed is not None:
             self.generator = torch.Generator(device=self.device)
@@ -238,6 +311,75 @@ class ShardedReplay:
         index draws (the counter is bumped once per update by the fused
         Adam prolog kernel)."""
         self._rng_ctr = ctr
+
+    # -- prioritized replay ----------------------------------------------
+    def _per_native(self):
+        """The extension if the priority kernels run (GPU, native on)."""
+        if self.device.type == "cuda":
+            from ..ops import native, native_enabled
+            if native_enabled():
+                return native()
+        return None
+
+    def _per_state(self):
+        return (self.per_prio, self.per_bsum, self.per_total, self.per_max)
+
+    def _per_ingest(self, t: int, start: int, rows: int) -> None:
+        """Rows ``[start, start + rows) mod cap`` of shard t were written:
+        they receive the shard's running maximum priority (read on the
+        device, never on the host)."""
+        ext = self._per_native()
+        if ext is not None:
+            ext.per_ingest_range(*self._per_state(), self._per_ws, t,
+                                 int(start), int(rows))
+        else:
+            from ..ops import torch_ref
+            torch_ref.per_ingest_(*self._per_state(), t, start, rows)
+
+    def set_per_beta(self, beta: float) -> None:
+        """Change the importance-sampling exponent; the sampling kernel
+        reads it from device memory, so a captured update follows."""
+        if self.per_beta is None:
+            raise RuntimeError("set_per_beta needs sampling='prioritized'")
+        if not 0.0 <= float(beta) <= 1.0:
+            raise ValueError(f"per_beta must be in [0, 1], got {beta!r}")
+        self.per_beta.fill_(float(beta))
+
+    def anneal_per_beta(self, grad_steps: int) -> float:
+        """Linear anneal from ``per_beta`` to 1.0 over
+        ``per_beta_anneal_steps`` gradient steps (0: constant)."""
+        beta = self.per_beta0
+        if self.per_beta_anneal_steps > 0:
+            f = min(1.0, max(0.0, grad_steps / self.per_beta_anneal_steps))
+            beta = self.per_beta0 + f * (1.0 - self.per_beta0)
+        self.set_per_beta(beta)
+        return beta
+
+    @torch.no_grad()
+    def update_priorities(self, indices: torch.Tensor,
+                          new_priorities: torch.Tensor,
+                          _zeroed: bool = False) -> None:
+        """Write new priorities back: ``indices`` are the flat row indices
+        a prioritized ``sample()`` returned, ``new_priorities`` one value
+        each.  A row listed more than once keeps the maximum of its values;
+        the shard's running maximum is raised; block sums and totals are
+        re-summed.  Capturable (no host round trip on the GPU path)."""
+        if self.per_prio is None:
+            raise RuntimeError("update_priorities needs "
+                               "sampling='prioritized'")
+        idx = indices.reshape(-1)
+        newp = new_priorities.reshape(-1)
+        if idx.numel() != newp.numel():
+            raise ValueError("one new priority per index")
+        ext = self._per_native()
+        if ext is None:
+            from ..ops import torch_ref
+            torch_ref.per_update_(*self._per_state(), idx, newp)
+            return
+        for o in range(0, idx.numel(), 8192):
+            ext.per_update(*self._per_state(), idx[o:o + 8192].contiguous(),
+                           newp[o:o + 8192].float().contiguous(),
+                           self._per_ws, _zeroed)
     def __len__(self) -> int:
         """min over shards (reference replay_buffers.__len__:102-107)."""
         return min(len(s) for s in self.shards)
@@ -468,10 +610,21 @@ class ShardedReplay:
             # host re-validation + launch on the current (main) stream
             native().replay_ingest(pair.dev, pair.host[:self._pk_hdr_words],
                                    *fields)
+            if self.per_prio is not None:
+                native().per_ingest_packed(
+                    pair.dev, pair.host[:self._pk_hdr_words],
+                    *self._per_state(), self._per_ws)
             pair.done_event.record()
             pair.scattered = True
         else:
             torch_ref.replay_ingest(pair.host[:b.used], *fields)
+            if self.per_prio is not None:
+                T, cap, Ds = self.f_states.shape
+                for d in torch_ref.packed_validate(
+                        pair.host[:b.used], T, cap, Ds,
+                        self.f_actions.shape[2]):
+                    torch_ref.per_ingest_(*self._per_state(), d[0], d[5],
+                                          d[3])
             pair.free = True
         for t, shard in enumerate(self.shards):
             shard.write_ptr, shard.size = b.post_wp[t], b.post_size[t]
@@ -572,6 +725,57 @@ class ShardedReplay:
         return {name: f.reshape(T * cap, -1).index_select(0, idx)
                 for name, f in zip(FIELDS, fields)}
 
+    def _sample_per(self, batch_size: int,
+                    graph_safe: bool) -> Dict[str, torch.Tensor]:
+        """Prioritized draw: the five fields plus ``indices`` (flat row
+        indices, int64 ``[B]``) and ``is_weights`` (raw, fp32 ``[B]``).
+        Rows are shard-major on every path (no concat shuffle)."""
+        T = self.num_tasks
+        cap = self.f_states.shape[1]
+        fields = (self.f_states, self.f_actions, self.f_rewards,
+                  self.f_next_states, self.f_dones)
+        if graph_safe and self.device.type == "cuda" \
+                and batch_size % T == 0:
+            from ..ops import native, native_enabled
+            if native_enabled():
+                if self._rng_ctr is None:
+                    raise RuntimeError(
+                        "sampling='prioritized' draws its graph-safe "
+                        "batches in k_replay_sample_per, which needs the "
+                        "engine's device rng counter: call attach_rng() "
+                        "(engine.capture does) and leave DSAC_KRNG at 1")
+                if batch_size > 8192:
+                    raise NotImplementedError(
+                        "sampling='prioritized': batches above 8192 rows "
+                        "are not supported on the GPU path")
+                idx = torch.empty(batch_size, dtype=torch.int64,
+                                  device=self.device)
+                w = torch.empty(batch_size, device=self.device)
+                o = native().replay_sample_per(
+                    *fields, self.sizes_dev, self.per_prio, self.per_bsum,
+                    self.per_total, self.per_beta, batch_size,
+                    self._rng_ctr, idx, w)
+                out = dict(zip(FIELDS, o))
+                out["indices"], out["is_weights"] = idx, w
+                return out
+        from ..ops import torch_ref
+        per = batch_size // T
+        ctr = self._rng_ctr
+        if ctr is None:
+            ctr = torch.randint(0, 1 << 62, (1,), device=self.device,
+                                generator=self.generator)
+        idx = torch_ref.per_sample_indices(
+            self.per_prio, self.per_bsum, self.per_total, self.sizes_dev,
+            batch_size, T, ctr)
+        w = torch_ref.per_is_weights(self.per_prio, self.per_total,
+                                     self.sizes_dev, idx, self.per_beta)
+        idx = idx + torch.arange(T, device=self.device) \
+            .repeat_interleave(per) * cap
+        out = {name: f.reshape(T * cap, -1).index_select(0, idx)
+               for name, f in zip(FIELDS, fields)}
+        out["indices"], out["is_weights"] = idx, w
+        return out
+
     @torch.no_grad()
     def sample(self, batch_size: int,
                graph_safe: bool = False) -> Dict[str, torch.Tensor]:
@@ -589,11 +793,19 @@ class ShardedReplay:
         distinct (while the shard holds at least ``batch_size //
         num_tasks`` rows): graph_safe=True on a GPU draws in
         ``k_replay_sample_norepl``, every other path with the same
-        algorithm in torch."""
+        algorithm in torch.
+
+        With ``sampling="prioritized"`` rows are drawn in proportion to
+        their priorities (``k_replay_sample_per`` for graph_safe=True on a
+        GPU, ``torch_ref.per_sample_indices`` elsewhere) and the batch
+        carries two more keys, ``indices`` and ``is_weights``; feed the
+        update's new priorities to :meth:`update_priorities`."""
         if self._pk_pending:
             self.flush_packed()
         if self.sampling == "without_replacement":
             return self._sample_norepl(batch_size, graph_safe)
+        if self.sampling == "prioritized":
+            return self._sample_per(batch_size, graph_safe)
         gen = None if graph_safe else self.generator
         if graph_safe and self.device.type == "cuda":
             from ..ops import has_native, native, native_enabled

@@ -66,8 +66,14 @@ class Learner:
         self.replay = ShardedReplay(cfg.buffer_size, num_tasks,
                                     cfg.mtobs_dim, cfg.action_dim,
                                     device=device, seed=seed,
-                                    sampling=sampling)
-        if self.replay.sampling == "without_replacement" \
+                                    sampling=sampling, **cfg.per_kwargs)
+        if self.replay.sampling == "prioritized":
+            if ddp is not None and ddp.enabled:
+                raise NotImplementedError(
+                    "sampling='prioritized' is not supported under "
+                    "data-parallel training")
+            self.engine.attach_per(self.replay)
+        if self.replay.sampling in ("without_replacement", "prioritized") \
                 and getattr(self.engine, "_use_krng", False):
             # the in-kernel draw is keyed by the engine's rng counter;
             # capture() attaches it too, the eager GPU path needs it here
@@ -378,6 +384,8 @@ class Learner:
             elif self._dp_graph_ready:  # pragma: no cover - multi-GPU
                 metrics_t = self.engine.dp_graphed_update()
             else:
+                # (a prioritized batch's new priorities are written back
+                # by the engine, to the replay attached above)
                 metrics_t = self.engine.update_tensors(
                     self.replay.sample(self.cfg.batch_size,
                                        graph_safe=self.device.type == "cuda"))
@@ -397,6 +405,10 @@ class Learner:
                                 update_iteration=self.iteration_counter)
             if self.grad_steps >= self._next_metric_tick:
                 self._next_metric_tick = self.grad_steps + self._metric_every
+                if self.replay.sampling == "prioritized":
+                    # a fill of the one-element device beta: the captured
+                    # sampler reads it, no re-capture
+                    self.replay.anneal_per_beta(self.grad_steps)
                 if self.device.type == "cuda":
                     # non-blocking tick: enqueue a D2H of the stat buffers
                     # into pinned staging and log the PREVIOUS tick's

@@ -56,7 +56,10 @@ class Trainer:
         self.replay = ShardedReplay(cfg.buffer_size, num_tasks,
                                     cfg.mtobs_dim, cfg.action_dim,
                                     device=device, seed=seed,
-                                    sampling=cfg.replay_sampling_choice)
+                                    sampling=cfg.replay_sampling_choice,
+                                    **cfg.per_kwargs)
+        if self.replay.sampling == "prioritized":
+            self.engine.attach_per(self.replay)
         env_fn = env_fn or default_env_fn
         envs, tasks = [], []
         for t in range(num_tasks):
