@@ -44,9 +44,11 @@ from .sac import SACEngine
 
 class CAREEngine(SACEngine):
     def __init__(self, cfg: SACConfig, device="cpu",
-                 precision: Optional[str] = None):
+                 precision: Optional[str] = None,
+                 max_grad_norm: Optional[float] = None):
         assert cfg.variant == "care" and cfg.encoder is not None
-        super().__init__(cfg, device, precision=precision)
+        super().__init__(cfg, device, precision=precision,
+                         max_grad_norm=max_grad_norm)
 
     # ------------------------------------------------------------------
     def _build_models(self) -> None:
@@ -264,10 +266,11 @@ class CAREEngine(SACEngine):
                 self.ddp.allreduce_grad_(self.context_group.flat_grad)
             self.context_encoder_optimizer.step()   # grads from critic bwd
         self.tie_actor_state_encoder()
-        return {"critic_loss": q_loss.detach(),
-                "actor_loss": policy_loss.detach(),
-                "alpha_loss": loss_log_alpha.detach(),
-                "entropy": entropy.detach()}
+        return self._clip_metrics({
+            "critic_loss": q_loss.detach(),
+            "actor_loss": policy_loss.detach(),
+            "alpha_loss": loss_log_alpha.detach(),
+            "entropy": entropy.detach()})
 
     # -- bf16 fast state-encoder machinery ------------------------------
     def _init_care_bf16(self) -> None:
@@ -504,10 +507,11 @@ class CAREEngine(SACEngine):
         if self.context_encoder_optimizer is not None:
             self.context_encoder_optimizer.step()
         self.tie_actor_state_encoder()
-        return {"critic_loss": q_loss.detach(),
-                "actor_loss": policy_loss.detach(),
-                "alpha_loss": loss_log_alpha.detach(),
-                "entropy": entropy.detach()}
+        return self._clip_metrics({
+            "critic_loss": q_loss.detach(),
+            "actor_loss": policy_loss.detach(),
+            "alpha_loss": loss_log_alpha.detach(),
+            "entropy": entropy.detach()})
 
 
     # -- hand-rolled backward (modified CARE, bf16) ----------------------
@@ -905,10 +909,11 @@ class CAREEngine(SACEngine):
                 pre_prologed=bool(st.get("prolog")))
         self.tie_actor_state_encoder()
         closs, al = st["closs"], st["al"]
-        return {"critic_loss": closs[6],  # summed in-kernel
-                "actor_loss": al[0],
-                "alpha_loss": al[2],
-                "entropy": al[3]}
+        return self._clip_metrics({
+            "critic_loss": closs[6],  # summed in-kernel
+            "actor_loss": al[0],
+            "alpha_loss": al[2],
+            "entropy": al[3]})
 
     @torch.no_grad()
     def publish_params(self) -> torch.Tensor:

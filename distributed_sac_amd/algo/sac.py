@@ -40,7 +40,8 @@ class SACEngine:
     """Holds models/optimizers and performs one SAC gradient update."""
 
     def __init__(self, cfg: SACConfig, device: torch.device | str = "cpu",
-                 precision: Optional[str] = None):
+                 precision: Optional[str] = None,
+                 max_grad_norm: Optional[float] = None):
         self.precision = (precision or
                           os.environ.get("DSAC_PRECISION", "fp32"))
         self.cfg = cfg
@@ -70,6 +71,44 @@ class SACEngine:
         self._per_zeroed = False
         self._build_models()
         self._build_optimizers()
+        self._init_grad_clip(max_grad_norm)
+
+    def _init_grad_clip(self, max_grad_norm: Optional[float]) -> None:
+        """Opt-in gradient-norm clipping: the argument, else the cfg's
+        ``max_grad_norm``, else ``DSAC_MAX_GRAD_NORM``, else off.  Critic,
+        actor and (CARE) context encoder are clipped each on its own norm,
+        as ``clip_grad_norm_`` per optimizer; alpha is guarded only.  All
+        groups bump ONE skip counter, the ``grad_skips`` metric."""
+        from ..ops.torch_ref import check_max_grad_norm
+        c = check_max_grad_norm(max_grad_norm)
+        if c is None:
+            c = self.cfg.max_grad_norm_choice
+        self.max_grad_norm = c
+        if c is None:
+            return
+        self._grad_skips = torch.zeros(1, dtype=torch.int32,
+                                       device=self.device)
+        self.critic_optimizer.set_max_grad_norm(c, self._grad_skips)
+        self.actor_optimizer.set_max_grad_norm(c, self._grad_skips)
+        self.log_alpha_optimizer.set_max_grad_norm(float("inf"),
+                                                   self._grad_skips)
+        ctx = getattr(self, "context_encoder_optimizer", None)
+        if ctx is not None:
+            ctx.set_max_grad_norm(c, self._grad_skips)
+
+    def _clip_metrics(self, out: Dict[str, torch.Tensor]):
+        """With clipping on, add the groups' gradient norms (of the
+        unclipped, all-reduced gradient) and the cumulative skip count:
+        views of device state the steps refresh in place."""
+        if self.max_grad_norm is None:
+            return out
+        out["critic_grad_norm"] = self.critic_optimizer.grad_norm
+        out["actor_grad_norm"] = self.actor_optimizer.grad_norm
+        ctx = getattr(self, "context_encoder_optimizer", None)
+        if ctx is not None:
+            out["context_grad_norm"] = ctx.grad_norm
+        out["grad_skips"] = self._grad_skips[0]
+        return out
 
     def _next_eps(self, like: torch.Tensor) -> torch.Tensor:
         if self._eps_queue:
@@ -534,12 +573,12 @@ class SACEngine:
         # --- Polyak target update -------------------------------------
         flat_polyak_(self.target_group, self.critic_group, self.tau)
 
-        return {
+        return self._clip_metrics({
             "critic_loss": q_loss.detach(),
             "actor_loss": policy_loss.detach(),
             "alpha_loss": loss_log_alpha.detach(),
             "entropy": entropy.detach(),
-        }
+        })
 
     def _actor_weights(self):
         if self.variant in ("sac", "vsac"):
@@ -822,12 +861,12 @@ class SACEngine:
         if not fuse:
             flat_polyak_(*polyak)
         closs, al = st["closs"], st["al"]
-        return {
+        return self._clip_metrics({
             "critic_loss": closs[6],  # summed in-kernel
             "actor_loss": al[0],
             "alpha_loss": al[2],
             "entropy": al[3],
-        }
+        })
 
     def _update_tensors_fused(self, batch):
         """GPU path: same math/order as update_tensors, restructured for
@@ -917,12 +956,12 @@ class SACEngine:
 
         flat_polyak_(self.target_group, self.critic_group, self.tau,
                      mirror=getattr(self, "_target_bf16", None))
-        return {
+        return self._clip_metrics({
             "critic_loss": q_loss.detach(),
             "actor_loss": policy_loss.detach(),
             "alpha_loss": loss_log_alpha.detach(),
             "entropy": entropy.detach(),
-        }
+        })
 
     # ------------------------------------------------------------------
     # hipGraph capture: the ENTIRE update (sample gather, forward, backward,

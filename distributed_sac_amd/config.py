@@ -108,6 +108,11 @@ class SACConfig:
     per_beta: float = 0.4
     per_beta_anneal_steps: int = 0
     per_eps: float = 1e-6
+    # net-new (the reference has none): clip each optimizer group's gradient
+    # to this global L2 norm and skip a group's step when its norm is not
+    # finite.  None (a cfg without the key) = off; inf = guard and metrics
+    # only.  See docs/KERNELS.md "Gradient-norm clipping".
+    max_grad_norm: Optional[float] = None
     # CARE-only block (reference cfg "encoder"):
     encoder: Optional[Dict[str, Any]] = None
     use_modified_care: bool = False
@@ -132,6 +137,23 @@ class SACConfig:
         if "replay_sampling" in self.raw or self.replay_sampling != "replace":
             return self.replay_sampling
         return None
+
+    @property
+    def max_grad_norm_choice(self) -> Optional[float]:
+        """``max_grad_norm`` if this cfg sets it, else the process-wide
+        default ``DSAC_MAX_GRAD_NORM`` (unset or empty: None, off)."""
+        from .ops.torch_ref import check_max_grad_norm
+        if self.max_grad_norm is not None:
+            return check_max_grad_norm(self.max_grad_norm)
+        env = os.environ.get("DSAC_MAX_GRAD_NORM", "")
+        if env == "":
+            return None
+        try:
+            v = float(env)
+        except ValueError:
+            raise ValueError(
+                f"DSAC_MAX_GRAD_NORM must be a positive number, got {env!r}")
+        return check_max_grad_norm(v)
 
     @property
     def per_kwargs(self) -> Dict[str, Any]:
@@ -198,6 +220,12 @@ class SACConfig:
                         "per_eps")}).items():
                 if k in cfg:
                     setattr(c, k, v)
+        if "max_grad_norm" in cfg:
+            from .ops.torch_ref import check_max_grad_norm
+            c.max_grad_norm = check_max_grad_norm(cfg["max_grad_norm"])
+            if c.max_grad_norm is None:
+                raise ValueError("max_grad_norm must be a positive number, "
+                                 "got None (leave the key out for off)")
         if "use_modified_care" in cfg:
             c.use_modified_care = bool(cfg["use_modified_care"])
         if "encoder" in cfg:

@@ -48,6 +48,11 @@ def main():
                              "prioritized"],
                     help="replay minibatch draw (default: the cfg's "
                          "replay_sampling, else DSAC_SAMPLING, else replace)")
+    ap.add_argument("--max-grad-norm", type=float, default=None,
+                    help="clip each optimizer group's gradient to this "
+                         "global L2 norm and skip non-finite steps (inf: "
+                         "guard only; default: the cfg's max_grad_norm, "
+                         "else DSAC_MAX_GRAD_NORM, else off)")
     # eval mode
     ap.add_argument("--eval", action="store_true")
     ap.add_argument("--checkpoint", default=None)
@@ -110,7 +115,8 @@ def main():
                             use_graph=not args.no_graph, ddp=ddp,
                             precision=args.precision,
                             eval_every_episodes=args.eval_every,
-                            sampling=args.sampling)
+                            sampling=args.sampling,
+                            max_grad_norm=args.max_grad_norm)
     stats = dt.run(max_grad_steps=args.max_grad_steps,
                    max_seconds=args.max_seconds)
     print(json.dumps(stats))

@@ -2239,6 +2239,132 @@ __global__ __launch_bounds__(256) void k_adam_multi_tail(
   if (mr != nullptr) mr[i] = f32_bf16_rne_d(pn);
 }
 
+// ---------------------------------------------------------------------------
+// Gradient-norm clipping (opt-in): K11 measures, K9d applies.
+//
+// K11: sum of squares of up to three flat gradients, one launch.  Grid
+// (GN_SLOTS, ranges) is FIXED, so the summation order depends on n alone:
+// block b of a range owns elements b*256+tid + k*GN_SLOTS*256 (k ascending,
+// one fp32 accumulator per thread), then wave_sum64, then the four wave
+// partials left to right, written to slot [range][b].  GN_SLOTS = 256 blocks
+// per range: 64 of them left three quarters of the CUs idle and made the
+// flagship's critic fold 100 us long.  No atomics; the
+// launch boundary orders the slots for K9d.  Range 0 may come as a split-K
+// arena: it is folded from 0.f in s order (k_reduce_arena), the folded
+// value stored to the flat gradient and squared.
+// ---------------------------------------------------------------------------
+constexpr int GN_SLOTS = 256;
+
+__global__ __launch_bounds__(256) void k_grad_sumsq(
+    float* g0, long n0, const float* g1, long n1, const float* g2, long n2,
+    const float* __restrict__ arena0, long stride0, int S0,
+    float* __restrict__ slots) {
+  __shared__ float s_w[4];
+  const int r = blockIdx.y, tid = threadIdx.x;
+  const float* g = r == 0 ? g0 : (r == 1 ? g1 : g2);
+  const long n = r == 0 ? n0 : (r == 1 ? n1 : n2);
+  const bool fold = r == 0 && arena0 != nullptr;
+  float acc = 0.f;
+  for (long i = (long)blockIdx.x * 256 + tid; i < n;
+       i += (long)GN_SLOTS * 256) {
+    float x;
+    if (fold) {
+      float a = 0.f;
+#pragma unroll 8
+      for (int s = 0; s < S0; ++s) a += arena0[(long)s * stride0 + i];
+      g0[i] = a;
+      x = a;
+    } else {
+      x = g[i];
+    }
+    acc += x * x;
+  }
+  acc = wave_sum64(acc);
+  if ((tid & 63) == 0) s_w[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0)
+    slots[r * GN_SLOTS + blockIdx.x] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+}
+
+// K9d: k_adam_multi_tail's index-range dispatch (<= 3 Adam groups + a
+// trailing Polyak range) on gradients that K11 measured.  Every block
+// re-sums each group's GN_SLOTS slots the same way (lane l adds slots l,
+// l+64, l+128, l+192 in that order, then wave_sum64), so all blocks derive
+// the same bits: s not finite -> the
+// group's threads leave p, m, v and the mirror alone; else
+// coef = min(1, c / (sqrtf(s) + 1e-6)) (torch clip_grad_norm_) and Adam runs
+// on coef * g — coef == 1.f leaves the arithmetic of k_adam_multi.  The flat
+// gradient is only read.  Block 0 publishes cs = {norm, coef, s} and bumps
+// the group's skip counter.
+__global__ __launch_bounds__(256) void k_adam_multi_clip(
+    float* p0, const float* g0, float* m0, float* v0, const float* st0, long n0,
+    float* p1, const float* g1, float* m1, float* v1, const float* st1, long n1,
+    float* p2, const float* g2, float* m2, float* v2, const float* st2, long n2,
+    float b1, float b2, float eps, unsigned short* mr0, unsigned short* mr1,
+    unsigned short* mr2, const float* __restrict__ slots,
+    float c0, float c1, float c2, float* cs0, float* cs1, float* cs2,
+    int* sk0, int* sk1, int* sk2,
+    float* __restrict__ pt, const float* __restrict__ psrc, long np,
+    float tau, unsigned short* __restrict__ pmir) {
+  __shared__ float s_coef[3];   // < 0: skip
+  const int tid = threadIdx.x, wv = tid >> 6;
+  if (wv < 3) {
+    const long nw = wv == 0 ? n0 : (wv == 1 ? n1 : n2);
+    if (nw > 0) {   // wave-uniform
+      const float* sl = slots + wv * GN_SLOTS + (tid & 63);
+      const float s = wave_sum64(((sl[0] + sl[64]) + sl[128]) + sl[192]);
+      if ((tid & 63) == 0) {
+        const float c = wv == 0 ? c0 : (wv == 1 ? c1 : c2);
+        const bool ok = fabsf(s) <= 3.402823466e+38f;   // false for NaN
+        const float norm = sqrtf(s);
+        const float coef = ok ? fminf(1.f, c / (norm + 1e-6f)) : -1.f;
+        s_coef[wv] = coef;
+        if (blockIdx.x == 0) {
+          float* cs = wv == 0 ? cs0 : (wv == 1 ? cs1 : cs2);
+          int* sk = wv == 0 ? sk0 : (wv == 1 ? sk1 : sk2);
+          cs[0] = norm; cs[1] = ok ? coef : 0.f; cs[2] = s;
+          // groups of one launch may share a counter: the three bumps are
+          // lanes of different waves, so go through the atomic unit
+          if (!ok) atomicAdd(sk, 1);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  long i = (long)blockIdx.x * blockDim.x + tid;
+  float* p; const float* g; float* m; float* v; const float* st;
+  unsigned short* mr; float coef;
+  if (i < n0) {
+    p = p0; g = g0; m = m0; v = v0; st = st0; mr = mr0; coef = s_coef[0];
+  }
+  else if ((i -= n0) < n1) {
+    p = p1; g = g1; m = m1; v = v1; st = st1; mr = mr1; coef = s_coef[1];
+  }
+  else if ((i -= n1) < n2) {
+    p = p2; g = g2; m = m2; v = v2; st = st2; mr = mr2; coef = s_coef[2];
+  }
+  else if ((i -= n2) < np) {
+    const float tn = __fmaf_rn(1.f - tau, pt[i], tau * psrc[i]);
+    pt[i] = tn;
+    if (pmir != nullptr) pmir[i] = f32_bf16_rne_d(tn);
+    return;
+  }
+  else return;
+  if (coef < 0.f) return;
+  // The Adam and Polyak expressions of k_adam_multi[_tail], with the
+  // roundings written out as the compiler contracts them there (which
+  // product fuses into the fma is its choice, and the extra multiply in
+  // front changes it): this kernel must give those kernels' bits.
+  const float gi = coef * g[i];
+  const float mi = __fmaf_rn(1.f - b1, gi, b1 * m[i]);
+  const float vi = __fmaf_rn(gi, (1.f - b2) * gi, b2 * v[i]);
+  m[i] = mi;
+  v[i] = vi;
+  const float pn = p[i] - st[1] * mi / __fmaf_rn(sqrtf(vi), st[2], eps);
+  p[i] = pn;
+  if (mr != nullptr) mr[i] = f32_bf16_rne_d(pn);
+}
+
 // ===========================================================================
 // Host wrappers
 // ===========================================================================
@@ -3083,6 +3209,143 @@ static void adam_step_multi_(std::vector<torch::Tensor> ps,
                      (float)b1, (float)b2, (float)eps, MR[0], MR[1], MR[2]);
 }
 
+// K11 alone: slots[r*GN_SLOTS + b] for r < gs.size(); arena0 as in
+// adam_step_multi_ (folded into gs[0], which is then written).
+static void grad_sumsq_(std::vector<torch::Tensor> gs, torch::Tensor slots,
+                        c10::optional<torch::Tensor> arena0 = c10::nullopt,
+                        long S0 = 0) {
+  const size_t G = gs.size();
+  TORCH_CHECK(G >= 1 && G <= 3, "1..3 ranges");
+  CHECK_IN(slots);
+  TORCH_CHECK(slots.is_contiguous() && slots.numel() >= 3 * GN_SLOTS,
+              "slots must hold 3 * 256 floats");
+  float* Gp[3] = {nullptr, nullptr, nullptr};
+  long N[3] = {0, 0, 0};
+  for (size_t g = 0; g < G; ++g) {
+    CHECK_IN(gs[g]);
+    TORCH_CHECK(gs[g].is_contiguous(), "flat gradients must be contiguous");
+    Gp[g] = gs[g].data_ptr<float>();
+    N[g] = gs[g].numel();
+  }
+  const float* ap = nullptr;
+  long stride = 0;
+  if (arena0.has_value() && arena0->defined() && arena0->numel() > 0) {
+    CHECK_IN(*arena0);
+    TORCH_CHECK(arena0->dim() == 2 && arena0->is_contiguous()
+                && arena0->size(1) == N[0] && S0 >= 1
+                && S0 <= arena0->size(0), "arena0 must be [>=S0, numel0]");
+    ap = arena0->data_ptr<float>();
+    stride = N[0];
+  }
+  hipLaunchKernelGGL(k_grad_sumsq, dim3(GN_SLOTS, (unsigned)G), dim3(256), 0,
+                     cur_stream(), Gp[0], N[0], Gp[1], N[1], Gp[2], N[2],
+                     ap, stride, (int)S0, slots.data_ptr<float>());
+}
+
+// adam_step_multi_ with gradient-norm clipping: [prolog,] K11, K9d.
+// maxn[g]: the group's threshold (inf = guard only); clip_states[g]: fp32
+// {norm, coef, s}; skips[g]: int32 counter (groups may share one).
+static void adam_step_clip_(std::vector<torch::Tensor> ps,
+                            std::vector<torch::Tensor> gs,
+                            std::vector<torch::Tensor> ms,
+                            std::vector<torch::Tensor> vs,
+                            std::vector<torch::Tensor> states,
+                            std::vector<double> lrs, double b1, double b2,
+                            double eps, std::vector<torch::Tensor> mirs,
+                            torch::Tensor slots, std::vector<double> maxn,
+                            std::vector<torch::Tensor> clip_states,
+                            std::vector<torch::Tensor> skips,
+                            c10::optional<torch::Tensor> rng = c10::nullopt,
+                            long skip_prolog = 0,
+                            c10::optional<torch::Tensor> arena0 = c10::nullopt,
+                            long S0 = 0,
+                            c10::optional<torch::Tensor> polyak_t = c10::nullopt,
+                            c10::optional<torch::Tensor> polyak_s = c10::nullopt,
+                            double tau = 0.0,
+                            c10::optional<torch::Tensor> polyak_mir = c10::nullopt) {
+  const size_t G = ps.size();
+  TORCH_CHECK(G >= 1 && G <= 3, "1..3 groups");
+  TORCH_CHECK(gs.size() == G && ms.size() == G && vs.size() == G
+              && states.size() == G && lrs.size() == G && maxn.size() == G
+              && clip_states.size() == G && skips.size() == G,
+              "one entry per group");
+  float* P[3] = {nullptr, nullptr, nullptr};
+  const float* Gr[3] = {nullptr, nullptr, nullptr};
+  float* M[3] = {nullptr, nullptr, nullptr};
+  float* V[3] = {nullptr, nullptr, nullptr};
+  float* St[3] = {nullptr, nullptr, nullptr};
+  float* CS[3] = {nullptr, nullptr, nullptr};
+  int* SK[3] = {nullptr, nullptr, nullptr};
+  float C[3] = {0.f, 0.f, 0.f};
+  long N[3] = {0, 0, 0};
+  double LR[3] = {0, 0, 0};
+  unsigned short* MR[3] = {nullptr, nullptr, nullptr};
+  long total = 0;
+  for (size_t g = 0; g < G; ++g) {
+    CHECK_IN(ps[g]); CHECK_IN(gs[g]); CHECK_IN(ms[g]); CHECK_IN(vs[g]);
+    CHECK_IN(states[g]); CHECK_IN(clip_states[g]);
+    N[g] = ps[g].numel();
+    TORCH_CHECK(gs[g].numel() == N[g] && ms[g].numel() == N[g]
+                && vs[g].numel() == N[g] && gs[g].is_contiguous()
+                && states[g].numel() >= 3 && clip_states[g].numel() >= 3
+                && skips[g].is_cuda() && skips[g].numel() >= 1
+                && skips[g].scalar_type() == torch::kInt32
+                && maxn[g] > 0.0, "bad clipped Adam group");
+    P[g] = ps[g].data_ptr<float>();
+    Gr[g] = gs[g].data_ptr<float>();
+    M[g] = ms[g].data_ptr<float>();
+    V[g] = vs[g].data_ptr<float>();
+    St[g] = states[g].data_ptr<float>();
+    CS[g] = clip_states[g].data_ptr<float>();
+    SK[g] = skips[g].data_ptr<int>();
+    C[g] = (float)maxn[g];
+    LR[g] = lrs[g];
+    if (g < mirs.size() && mirs[g].defined() && mirs[g].numel() > 0) {
+      TORCH_CHECK(mirs[g].numel() == N[g]
+                  && mirs[g].scalar_type() == torch::kBFloat16);
+      MR[g] = (unsigned short*)mirs[g].data_ptr();
+    }
+    total += N[g];
+  }
+  long long* rng_p = (rng.has_value() && rng->numel() > 0)
+      ? (long long*)rng->data_ptr<long>() : nullptr;
+  if (!skip_prolog)
+    hipLaunchKernelGGL(k_adam_prolog3, dim3(1), dim3(3), 0, cur_stream(),
+                       rng_p, St[0], St[1], St[2], (float)LR[0],
+                       (float)LR[1], (float)LR[2], (float)b1, (float)b2);
+  grad_sumsq_(gs, slots, arena0, S0);
+  float* pt = nullptr; const float* psrc = nullptr; long np = 0;
+  unsigned short* pmir = nullptr;
+  if (polyak_t.has_value() && polyak_t->defined() && polyak_t->numel() > 0) {
+    TORCH_CHECK(polyak_s.has_value(), "polyak source missing");
+    CHECK_IN(*polyak_t); CHECK_IN(*polyak_s);
+    np = polyak_t->numel();
+    TORCH_CHECK(polyak_s->numel() == np && polyak_t->is_contiguous()
+                && polyak_s->is_contiguous(), "polyak buffers must match");
+    for (size_t g = 0; g < G; ++g)
+      TORCH_CHECK(polyak_s->data_ptr() != ps[g].data_ptr()
+                  && polyak_t->data_ptr() != ps[g].data_ptr(),
+                  "polyak buffers must not be stepped in the same launch");
+    pt = polyak_t->data_ptr<float>();
+    psrc = polyak_s->data_ptr<float>();
+    if (polyak_mir.has_value() && polyak_mir->defined()
+        && polyak_mir->numel() > 0) {
+      TORCH_CHECK(polyak_mir->numel() == np
+                  && polyak_mir->scalar_type() == torch::kBFloat16);
+      pmir = (unsigned short*)polyak_mir->data_ptr();
+    }
+  }
+  hipLaunchKernelGGL(k_adam_multi_clip, dim3((total + np + 255) / 256),
+                     dim3(256), 0, cur_stream(),
+                     P[0], Gr[0], M[0], V[0], St[0], N[0],
+                     P[1], Gr[1], M[1], V[1], St[1], N[1],
+                     P[2], Gr[2], M[2], V[2], St[2], N[2],
+                     (float)b1, (float)b2, (float)eps, MR[0], MR[1], MR[2],
+                     slots.data_ptr<float>(), C[0], C[1], C[2],
+                     CS[0], CS[1], CS[2], SK[0], SK[1], SK[2],
+                     pt, psrc, np, (float)tau, pmir);
+}
+
 static void polyak_(torch::Tensor t, torch::Tensor s, double tau,
                     c10::optional<torch::Tensor> mir_opt) {
   CHECK_IN(t);
@@ -3484,6 +3747,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           pybind11::arg("vs"), pybind11::arg("states"), pybind11::arg("lrs"),
           pybind11::arg("b1"), pybind11::arg("b2"), pybind11::arg("eps"),
           pybind11::arg("mirs") = std::vector<torch::Tensor>(),
+          pybind11::arg("rng") = pybind11::none(),
+          pybind11::arg("skip_prolog") = 0,
+          pybind11::arg("arena0") = pybind11::none(),
+          pybind11::arg("S0") = 0,
+          pybind11::arg("polyak_t") = pybind11::none(),
+          pybind11::arg("polyak_s") = pybind11::none(),
+          pybind11::arg("tau") = 0.0,
+          pybind11::arg("polyak_mir") = pybind11::none());
+  mod.def("grad_sumsq_", &grad_sumsq_,
+          pybind11::arg("gs"), pybind11::arg("slots"),
+          pybind11::arg("arena0") = pybind11::none(),
+          pybind11::arg("S0") = 0);
+  mod.def("adam_step_clip_", &adam_step_clip_,
+          pybind11::arg("ps"), pybind11::arg("gs"), pybind11::arg("ms"),
+          pybind11::arg("vs"), pybind11::arg("states"), pybind11::arg("lrs"),
+          pybind11::arg("b1"), pybind11::arg("b2"), pybind11::arg("eps"),
+          pybind11::arg("mirs"), pybind11::arg("slots"),
+          pybind11::arg("maxn"), pybind11::arg("clip_states"),
+          pybind11::arg("skips"),
           pybind11::arg("rng") = pybind11::none(),
           pybind11::arg("skip_prolog") = 0,
           pybind11::arg("arena0") = pybind11::none(),

@@ -22,7 +22,7 @@ from typing import Dict, Iterable, List, Optional
 import torch
 import torch.nn as nn
 
-from . import has_native, native, native_enabled
+from . import has_native, native, native_enabled, torch_ref
 
 
 def _flatten_into(params: List[torch.Tensor]) -> torch.Tensor:
@@ -127,7 +127,8 @@ class FusedAdam:
     """
 
     def __init__(self, group: FlatParams, lr: float,
-                 betas=(0.9, 0.999), eps: float = 1e-8, ref_params=None):
+                 betas=(0.9, 0.999), eps: float = 1e-8, ref_params=None,
+                 max_grad_norm: Optional[float] = None):
         self.group = group
         # (de)serialization order: the reference checkpoints index optimizer
         # state by the REFERENCE's parameter order (e.g. chain(critic1,
@@ -154,6 +155,76 @@ class FusedAdam:
         self.bf16_mirror: Optional[torch.Tensor] = None
         if group.flat_data.is_cuda and native_enabled() and has_native():
             self._dev_state = torch.zeros(3, device=group.flat_data.device)
+        # gradient-norm clipping (None = off): fp32 {norm, coef, s} of the
+        # last step, the int32 skip counter and, for the HIP path, the
+        # sum-of-squares partial slots (3 ranges x 256 blocks)
+        self.max_grad_norm: Optional[float] = None
+        self._clip_state: Optional[torch.Tensor] = None
+        self._skips: Optional[torch.Tensor] = None
+        self._clip_slots: Optional[torch.Tensor] = None
+        self.set_max_grad_norm(max_grad_norm)
+
+    def set_max_grad_norm(self, max_grad_norm: Optional[float],
+                          skips: Optional[torch.Tensor] = None) -> None:
+        """Clip this group's gradient to a global L2 norm of
+        ``max_grad_norm`` inside :meth:`step` / :meth:`step_many` and skip
+        the step when the norm is not finite (``inf``: guard only; ``None``:
+        off).  The flat gradient itself stays unclipped.  A skipped step
+        still advances the step counter: bias correction counts ATTEMPTED
+        steps.  ``skips``: int32 [1] counter to bump instead of this
+        optimizer's own, so several optimizers can share one."""
+        self.max_grad_norm = torch_ref.check_max_grad_norm(max_grad_norm)
+        if self.max_grad_norm is None:
+            return
+        dev = self.group.flat_data.device
+        if self._clip_state is None:
+            self._clip_state = torch.tensor([0.0, 1.0, 0.0], device=dev)
+            self._skips = torch.zeros(1, dtype=torch.int32, device=dev)
+            if self._dev_state is not None:
+                self._clip_slots = torch.zeros(3 * 256, device=dev)
+        if skips is not None:
+            assert skips.dtype == torch.int32 and skips.device == dev
+            self._skips = skips
+
+    @property
+    def grad_norm(self) -> Optional[torch.Tensor]:
+        """L2 norm of the last step's unclipped gradient (0-d view)."""
+        return None if self._clip_state is None else self._clip_state[0]
+
+    @property
+    def clip_coef(self) -> Optional[torch.Tensor]:
+        """Factor the last step applied (1 = unclipped, 0 = skipped)."""
+        return None if self._clip_state is None else self._clip_state[1]
+
+    @property
+    def grad_skips(self) -> Optional[torch.Tensor]:
+        """Cumulative number of skipped steps (0-d int32 view)."""
+        return None if self._skips is None else self._skips[0]
+
+    def _step_clip_native(self, opts, rng_bump, pre_prologed, arena0,
+                          polyak) -> None:
+        args = [
+            [o.group.flat_data for o in opts],
+            [o.group.flat_grad for o in opts],
+            [o.exp_avg for o in opts],
+            [o.exp_avg_sq for o in opts],
+            [o._dev_state for o in opts],
+            [o.lr for o in opts],
+            self.betas[0], self.betas[1], self.eps,
+            [o.bf16_mirror if o.bf16_mirror is not None
+             else torch.Tensor() for o in opts],
+            self._clip_slots,
+            [o.max_grad_norm for o in opts],
+            [o._clip_state for o in opts],
+            [o._skips for o in opts],
+            rng_bump, 1 if pre_prologed else 0,
+            arena0[0] if arena0 is not None else None,
+            int(arena0[1]) if arena0 is not None else 0]
+        if polyak is not None:
+            target, source, tau, mirror = polyak
+            assert target.numel == source.numel
+            args += [target.flat_data, source.flat_data, float(tau), mirror]
+        native().adam_step_clip_(*args)
 
     @property
     def step_count(self) -> int:
@@ -180,6 +251,10 @@ class FusedAdam:
         m, v = self.exp_avg, self.exp_avg_sq
         b1, b2 = self.betas
         if self._dev_state is not None:
+            if self.max_grad_norm is not None:
+                self._step_clip_native([self], None, pre_prologed, arena,
+                                       None)
+                return
             if arena is not None:
                 native().adam_step_dev_(p, g, m, v, self._dev_state,
                                         self.lr, b1, b2, self.eps,
@@ -197,6 +272,14 @@ class FusedAdam:
             for s in range(int(arena[1])):
                 g.add_(arena[0][s])
         self._step_count += 1
+        if self.max_grad_norm is not None:
+            sq, norm, coef, ok = torch_ref.grad_clip_coef(
+                g, self.max_grad_norm)
+            self._clip_state.copy_(torch.stack([norm, coef, sq]))
+            if not bool(ok):
+                self._skips.add_(1)
+                return
+            g = g * coef   # the flat gradient stays unclipped
         bc1 = 1 - b1 ** self._step_count
         bc2 = 1 - b2 ** self._step_count
         m.mul_(b1).add_(g, alpha=1 - b1)
@@ -229,6 +312,12 @@ class FusedAdam:
                 and all(o._dev_state is not None for o in live)
                 and all(o.betas == live[0].betas and o.eps == live[0].eps
                         for o in live)):
+            if any(o.max_grad_norm is not None for o in live):
+                assert all(o.max_grad_norm is not None for o in live), \
+                    "clipping is per launch: set it on every optimizer"
+                live[0]._step_clip_native(live, rng_bump, pre_prologed,
+                                          arena0, polyak)
+                return
             args = [
                 [o.group.flat_data for o in live],
                 [o.group.flat_grad for o in live],

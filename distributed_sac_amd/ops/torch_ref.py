@@ -527,3 +527,39 @@ def per_ingest_(prio: torch.Tensor, bsum: torch.Tensor, total: torch.Tensor,
          + int(start)) % cap
     prio[t, r] = max_prio[t]
     _per_resum_blocks(prio, bsum, total, t, r)
+
+
+# ---------------------------------------------------------------------------
+# Gradient-norm clipping (docs/KERNELS.md "Gradient-norm clipping").
+# ---------------------------------------------------------------------------
+
+def check_max_grad_norm(v):
+    """``None`` (off) or a positive number, ``inf`` included (guard and
+    metrics only); anything else raises ValueError.  Returns a float."""
+    if v is None:
+        return None
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        raise ValueError(f"max_grad_norm must be a positive number, got {v!r}")
+    v = float(v)
+    if not v > 0.0:   # also NaN
+        raise ValueError(f"max_grad_norm must be a positive number, got {v!r}")
+    return v
+
+
+@torch.no_grad()
+def grad_clip_coef(g: torch.Tensor, max_norm: float):
+    """``(s, norm, coef, ok)`` of one flat fp32 gradient, as 0-d tensors:
+    ``s = sum g_i^2``, ``norm = sqrt(s)``, ``ok = isfinite(s)`` and
+    ``coef = min(1, max_norm / (norm + 1e-6))`` — the formula of
+    ``torch.nn.utils.clip_grad_norm_`` — or 0 where the step is skipped."""
+    g = g.reshape(-1).to(torch.float32)
+    s = (g * g).sum()
+    # correctly rounded, as sqrtf (torch's fp32 CPU sqrt is not always)
+    norm = s.double().sqrt().float()
+    ok = torch.isfinite(s)
+    # fp32 operands throughout: the kernel's arithmetic, bit for bit
+    c, tiny = (torch.tensor(x, dtype=torch.float32, device=g.device)
+               for x in (float(max_norm), 1e-6))
+    coef = torch.where(ok, (c / (norm + tiny)).clamp(max=1.0),
+                       torch.zeros_like(norm))
+    return s, norm, coef, ok

@@ -45,7 +45,8 @@ class Learner:
                  heartbeat_timeout: float = 60.0, rings=None,
                  precision: str = None, publish_interval_s: float = 0.02,
                  graph_chunk: int = 4, ingest: Optional[str] = None,
-                 sampling: Optional[str] = None):
+                 sampling: Optional[str] = None,
+                 max_grad_norm: Optional[float] = None):
         self.cfg = cfg
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -55,7 +56,10 @@ class Learner:
         if precision is None:
             precision = "bf16" if torch.device(device).type == "cuda" \
                 else "fp32"
-        self.engine = create_engine(cfg, device, precision=precision)
+        # gradient-norm clipping: the argument, else the cfg's
+        # max_grad_norm, else DSAC_MAX_GRAD_NORM, else off
+        self.engine = create_engine(cfg, device, precision=precision,
+                                    max_grad_norm=max_grad_norm)
         if ddp is not None:
             self.engine.attach_ddp(ddp)
         num_tasks = cfg.num_tasks if cfg.variant in ("mtsac", "care") else 1

@@ -52,7 +52,8 @@ class DistributedTrainer:
                  ddp=None, transport: str = "auto", precision: str = None,
                  eval_every_episodes: int = 0,
                  ingest: Optional[str] = None,
-                 sampling: Optional[str] = None):
+                 sampling: Optional[str] = None,
+                 max_grad_norm: Optional[float] = None):
         self.cfg = cfg
         self.env_fn = env_fn or default_env_fn
         self.ctx = mp.get_context("spawn")
@@ -94,7 +95,8 @@ class DistributedTrainer:
                                use_graph=use_graph, ddp=ddp, seed=seed,
                                heartbeat=self.heartbeat, rings=self.rings,
                                precision=precision, ingest=ingest,
-                               sampling=sampling)
+                               sampling=sampling,
+                               max_grad_norm=max_grad_norm)
 
     def _spawn_player(self, pid: int, seed_bump: int = 0) -> "mp.Process":
         p = self.ctx.Process(

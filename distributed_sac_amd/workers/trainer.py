@@ -46,12 +46,13 @@ class Trainer:
     def __init__(self, cfg: SACConfig, device: str = "cpu",
                  env_fn: Optional[Callable] = None,
                  envs_per_task: int = 1, seed: int = 0,
-                 logger: Optional[MetricLogger] = None):
+                 logger: Optional[MetricLogger] = None,
+                 max_grad_norm: Optional[float] = None):
         self.cfg = cfg
         self.device = torch.device(device)
         if self.device.type != "cuda":
             torch.set_num_threads(1)   # tiny ops thrash the intra-op pool
-        self.engine = create_engine(cfg, device)
+        self.engine = create_engine(cfg, device, max_grad_norm=max_grad_norm)
         num_tasks = cfg.num_tasks if cfg.variant in ("mtsac", "care") else 1
         self.replay = ShardedReplay(cfg.buffer_size, num_tasks,
                                     cfg.mtobs_dim, cfg.action_dim,
