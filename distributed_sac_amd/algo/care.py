@@ -38,7 +38,7 @@ from ..models.context_encoder import contextEncoder
 from ..ops import functional as Fops
 from ..ops.chain import (ManualChain, forward_pair, mlp_bwd_arena,
                          pack_chains)
-from ..ops.flat import FlatParams, FusedAdam
+from ..ops.flat import FlatParams, FusedAdam, polyak_flat_
 from .sac import SACEngine
 
 
@@ -176,23 +176,8 @@ class CAREEngine(SACEngine):
         t, s = self.target_group.flat_data, self.critic_group.flat_data
         m0 = mirror[:se] if mirror is not None else None
         m1 = mirror[se:] if mirror is not None else None
-        self._polyak_slice(t[:se], s[:se], self.se_tau, m0)
-        self._polyak_slice(t[se:], s[se:], self.tau, m1)
-
-    @staticmethod
-    @torch.no_grad()
-    def _polyak_slice(t: torch.Tensor, s: torch.Tensor, tau: float,
-                      mirror=None) -> None:
-        from ..ops import has_native, native, native_enabled
-        if t.is_cuda and native_enabled() and has_native():
-            if mirror is not None:
-                native().polyak_(t, s, float(tau), mirror)
-            else:
-                native().polyak_(t, s, float(tau))
-            return
-        t.mul_(1.0 - tau).add_(s, alpha=tau)
-        if mirror is not None:
-            mirror.copy_(t)
+        polyak_flat_(t[:se], s[:se], self.se_tau, m0)
+        polyak_flat_(t[se:], s[se:], self.tau, m1)
 
     # ------------------------------------------------------------------
     def _sample_care(self, mtobss, z_context, detach_z_encs=False):
@@ -497,8 +482,7 @@ class CAREEngine(SACEngine):
         (policy_loss + loss_log_alpha).backward()
         if self.ddp is not None:
             self.ddp.allreduce_grad_(self._aa_arena)
-        from ..ops.flat import FusedAdam as _FA
-        _FA.step_many([self.actor_optimizer, self.log_alpha_optimizer])
+        FusedAdam.step_many([self.actor_optimizer, self.log_alpha_optimizer])
         self.refresh_bf16("actor")
         self.alpha = self.log_alpha.exp().detach()
 
@@ -893,13 +877,12 @@ class CAREEngine(SACEngine):
 
     @torch.no_grad()
     def _manual_seg3(self):
-        from ..ops.flat import FusedAdam as _FA
         st = self._dp_st
-        _FA.step_many([self.actor_optimizer, self.log_alpha_optimizer],
-                      rng_bump=(None if st.get("prolog")
-                                else (self._rng_ctr if self._use_krng
-                                      else None)),
-                      pre_prologed=bool(st.get("prolog")))
+        FusedAdam.step_many(
+            [self.actor_optimizer, self.log_alpha_optimizer],
+            rng_bump=(None if st.get("prolog")
+                      else (self._rng_ctr if self._use_krng else None)),
+            pre_prologed=bool(st.get("prolog")))
         # self.alpha refreshed lazily outside the graph (see SACEngine)
         self._polyak_targets(mirror=self._target_bf16)
         self._refresh_mixT("target")

@@ -12,7 +12,8 @@
 //   K6  critic/actor/alpha loss — single-workgroup fused loss reductions
 //                              (incl. softmax(-alpha) task weights, per-task
 //                              alpha gather, entropy) with analytic backward
-//   K9  adam_step_[dev_]     — fused Adam over one flat parameter buffer
+//   K9  k_adam_groups        — fused Adam over up to three flat parameter
+//                              buffers (+ arena fold, clipping, Polyak range)
 //   K10 polyak_              — fused soft target update over flat buffers
 //   K12 replay_sample        — stratified gather from the HBM-resident
 //                              sharded replay in ONE kernel
@@ -379,7 +380,7 @@ __global__ __launch_bounds__(256) void k_reduce_partials(
 // ---------------------------------------------------------------------------
 // counter-based device RNG (splitmix64 hash of (counter, index, salt)):
 // every RNG-consuming kernel derives its noise from one persistent int64
-// counter that k_adam_prolog_many (or prolog3) bumps ONCE per update
+// counter that k_adam_prolog_many bumps ONCE per update
 // (single-block kernels, so the bump is race-free by stream ordering).
 // Replaces the per-update
 // torch rand/randn launches AND the hipGraph RNG-offset bookkeeping
@@ -1237,136 +1238,11 @@ __global__ __launch_bounds__(256) void k_squash_bwd2(
   }
 }
 
-// ---------------------------------------------------------------------------
-// K9: fused Adam over one flat buffer (torch.optim.Adam numerics).
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_adam(
-    float* __restrict__ p, const float* __restrict__ g,
-    float* __restrict__ m, float* __restrict__ v, long n,
-    float b1, float b2, float step_size, float inv_sqrt_bc2, float eps) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float gi = g[i];
-  const float mi = b1 * m[i] + (1.f - b1) * gi;
-  const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-  m[i] = mi;
-  v[i] = vi;
-  p[i] -= step_size * mi / (sqrtf(vi) * inv_sqrt_bc2 + eps);
-}
-
-// K9b: graph-capturable Adam — the step counter lives on-device so a
-// captured update's bias correction advances across hipGraph replays.
-__global__ void k_adam_prolog(float* __restrict__ state, float lr, float b1,
-                              float b2) {
-  const float step = state[0] + 1.f;
-  state[0] = step;
-  state[1] = lr / (1.f - __powf(b1, step));          // step_size
-  state[2] = 1.f / sqrtf(1.f - __powf(b2, step));    // inv_sqrt_bc2
-}
-
 __device__ __forceinline__ unsigned short f32_bf16_rne_d(float f) {
   union { float f; unsigned u; } v{f};
   unsigned u = v.u;
   u += 0x7FFFu + ((u >> 16) & 1u);
   return (unsigned short)(u >> 16);
-}
-
-// mir (optional): the group's bf16 compute mirror — emitting the refreshed
-// mirror from the SAME kernel kills the separate full-buffer cast launch.
-__global__ __launch_bounds__(256) void k_adam_dev(
-    float* __restrict__ p, const float* __restrict__ g,
-    float* __restrict__ m, float* __restrict__ v,
-    const float* __restrict__ state, long n, float b1, float b2, float eps,
-    unsigned short* __restrict__ mir) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float step_size = state[1], inv_sqrt_bc2 = state[2];
-  const float gi = g[i];
-  const float mi = b1 * m[i] + (1.f - b1) * gi;
-  const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-  m[i] = mi;
-  v[i] = vi;
-  const float pn = p[i] - step_size * mi / (sqrtf(vi) * inv_sqrt_bc2 + eps);
-  p[i] = pn;
-  if (mir != nullptr) mir[i] = f32_bf16_rne_d(pn);
-}
-
-// K9c: all three optimizer groups (critic was stepped earlier; this one
-// covers actor+alpha+optional context in ONE launch) — or any <=3 groups.
-struct AdamGroup {
-  float* p; const float* g; float* m; float* v; const float* st; long n;
-};
-
-// one launch advances EVERY optimizer's Adam state for this update
-// (critic + actor + alpha [+ context]) and bumps the device RNG counter:
-// the engine calls it once at the top of seg2, and the per-optimizer
-// steppers skip their own prologs (skip_prolog)
-__global__ void k_adam_prolog_many(long long* rng,
-                                   float* s0, float* s1, float* s2,
-                                   float* s3,
-                                   float lr0, float lr1, float lr2,
-                                   float lr3, float b1, float b2) {
-  if (rng != nullptr && threadIdx.x == 0) rng[0] += 1;
-  const int i = threadIdx.x;
-  float* sv[4] = {s0, s1, s2, s3};
-  const float lrv[4] = {lr0, lr1, lr2, lr3};
-  if (i >= 4 || sv[i] == nullptr) return;
-  float* st = sv[i];
-  const float step = st[0] + 1.f;
-  st[0] = step;
-  st[1] = lrv[i] / (1.f - __powf(b1, step));
-  st[2] = 1.f / sqrtf(1.f - __powf(b2, step));
-}
-
-__global__ void k_adam_prolog3(long long* rng, float* s0, float* s1,
-                               float* s2,
-                               float lr0, float lr1, float lr2,
-                               float b1, float b2) {
-  if (rng != nullptr && threadIdx.x == 0) rng[0] += 1;
-  const int i = threadIdx.x;
-  float* s = i == 0 ? s0 : (i == 1 ? s1 : s2);
-  const float lr = i == 0 ? lr0 : (i == 1 ? lr1 : lr2);
-  if (s == nullptr) return;
-  const float step = s[0] + 1.f;
-  s[0] = step;
-  s[1] = lr / (1.f - __powf(b1, step));
-  s[2] = 1.f / sqrtf(1.f - __powf(b2, step));
-}
-
-__global__ __launch_bounds__(256) void k_adam_multi(
-    float* p0, const float* g0, float* m0, float* v0, const float* st0, long n0,
-    float* p1, const float* g1, float* m1, float* v1, const float* st1, long n1,
-    float* p2, const float* g2, float* m2, float* v2, const float* st2, long n2,
-    float b1, float b2, float eps, unsigned short* mr0, unsigned short* mr1,
-    unsigned short* mr2) {
-  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  float* p; const float* g; float* m; float* v; const float* st;
-  unsigned short* mr;
-  if (i < n0) { p = p0; g = g0; m = m0; v = v0; st = st0; mr = mr0; }
-  else if ((i -= n0) < n1) { p = p1; g = g1; m = m1; v = v1; st = st1; mr = mr1; }
-  else if ((i -= n1) < n2) { p = p2; g = g2; m = m2; v = v2; st = st2; mr = mr2; }
-  else return;
-  const float gi = g[i];
-  const float mi = b1 * m[i] + (1.f - b1) * gi;
-  const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-  m[i] = mi;
-  v[i] = vi;
-  const float pn = p[i] - st[1] * mi / (sqrtf(vi) * st[2] + eps);
-  p[i] = pn;
-  if (mr != nullptr) mr[i] = f32_bf16_rne_d(pn);
-}
-
-// ---------------------------------------------------------------------------
-// K10: t = (1-tau)*t + tau*s over flat buffers.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_polyak(
-    float* __restrict__ t, const float* __restrict__ s, long n, float tau,
-    unsigned short* __restrict__ mir) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float tn = (1.f - tau) * t[i] + tau * s[i];
-  t[i] = tn;
-  if (mir != nullptr) mir[i] = f32_bf16_rne_d(tn);
 }
 
 // ---------------------------------------------------------------------------
@@ -2167,116 +2043,128 @@ __global__ __launch_bounds__(256) void k_actor_alpha_loss_fwd_bwd(
   }
 }
 
-// K9b that folds the split-K arena itself: g = sum_s arena[s*stride+i] from
-// 0.f in s order (k_reduce_arena), written back to the flat gradient for
-// callers that read .grad, then the unchanged Adam math + mirror store.
-__global__ __launch_bounds__(256) void k_adam_dev_arena(
-    float* __restrict__ p, float* __restrict__ g,
-    float* __restrict__ m, float* __restrict__ v,
-    const float* __restrict__ state, long n, float b1, float b2, float eps,
-    unsigned short* __restrict__ mir, const float* __restrict__ arena,
-    long stride, int S) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float step_size = state[1], inv_sqrt_bc2 = state[2];
-  float acc = 0.f;
-  for (int s = 0; s < S; ++s) acc += arena[(long)s * stride + i];
-  g[i] = acc;
-  const float gi = acc;
-  const float mi = b1 * m[i] + (1.f - b1) * gi;
-  const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+// ---------------------------------------------------------------------------
+// K9 / K10 / K11: the optimizer tail.  adam_elem and polyak_elem are the
+// ONLY definitions of the two element updates; every path (host step size,
+// device step state, split-K arena, several groups, clipping, Polyak alone
+// or appended) calls them, so the paths cannot drift apart by a bit.
+// ---------------------------------------------------------------------------
+
+// torch.optim.Adam numerics on one element.  The rounding points are
+// explicit: left as plain C++, which product fuses into which fma is the
+// compiler's choice per kernel.
+__device__ __forceinline__ void adam_elem(
+    float* p, float* m, float* v, unsigned short* mir, long i, float gi,
+    float step_size, float inv_sqrt_bc2, float b1, float b2, float eps) {
+  const float m0 = m[i], v0 = v[i], p0 = p[i];   // loads ahead of the stores
+  const float mi = __fmaf_rn(1.f - b1, gi, b1 * m0);
+  const float vi = __fmaf_rn(gi, (1.f - b2) * gi, b2 * v0);
   m[i] = mi;
   v[i] = vi;
-  const float pn = p[i] - step_size * mi / (sqrtf(vi) * inv_sqrt_bc2 + eps);
+  const float pn =
+      p0 - step_size * mi / __fmaf_rn(sqrtf(vi), inv_sqrt_bc2, eps);
   p[i] = pn;
+  // the group's bf16 compute mirror, refreshed by the same thread: no
+  // separate full-buffer cast launch
   if (mir != nullptr) mir[i] = f32_bf16_rne_d(pn);
 }
 
-// K9c + K10 in one launch: the index-range dispatch of k_adam_multi with
-// (a) an optional split-K arena folded into group 0's gradient as above and
-// (b) a trailing Polyak range (pt <- (1-tau)*pt + tau*psrc, + bf16 mirror).
-// The Polyak source must not be one of the Adam groups of this launch.
-__global__ __launch_bounds__(256) void k_adam_multi_tail(
-    float* p0, float* g0, float* m0, float* v0, const float* st0, long n0,
-    float* p1, const float* g1, float* m1, float* v1, const float* st1, long n1,
-    float* p2, const float* g2, float* m2, float* v2, const float* st2, long n2,
-    float b1, float b2, float eps, unsigned short* mr0, unsigned short* mr1,
-    unsigned short* mr2, const float* __restrict__ arena0, long stride0,
-    int S0, float* __restrict__ pt, const float* __restrict__ psrc, long np,
-    float tau, unsigned short* __restrict__ pmir) {
-  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  float* p; const float* g; float* m; float* v; const float* st;
-  unsigned short* mr;
-  bool fold = false;
-  if (i < n0) {
-    p = p0; g = g0; m = m0; v = v0; st = st0; mr = mr0;
-    fold = arena0 != nullptr;
-  }
-  else if ((i -= n0) < n1) { p = p1; g = g1; m = m1; v = v1; st = st1; mr = mr1; }
-  else if ((i -= n1) < n2) { p = p2; g = g2; m = m2; v = v2; st = st2; mr = mr2; }
-  else if ((i -= n2) < np) {
-    const float tn = (1.f - tau) * pt[i] + tau * psrc[i];
-    pt[i] = tn;
-    if (pmir != nullptr) pmir[i] = f32_bf16_rne_d(tn);
-    return;
-  }
-  else return;
-  float gi;
-  if (fold) {
-    float acc = 0.f;
-    for (int s = 0; s < S0; ++s) acc += arena0[(long)s * stride0 + i];
-    g0[i] = acc;
-    gi = acc;
-  } else {
-    gi = g[i];
-  }
-  const float mi = b1 * m[i] + (1.f - b1) * gi;
-  const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-  m[i] = mi;
-  v[i] = vi;
-  const float pn = p[i] - st[1] * mi / (sqrtf(vi) * st[2] + eps);
-  p[i] = pn;
-  if (mr != nullptr) mr[i] = f32_bf16_rne_d(pn);
+// t = (1-tau)*t + tau*s, + bf16 mirror
+__device__ __forceinline__ void polyak_elem(
+    float* t, const float* s, unsigned short* mir, long i, float tau) {
+  const float tn = __fmaf_rn(1.f - tau, t[i], tau * s[i]);
+  t[i] = tn;
+  if (mir != nullptr) mir[i] = f32_bf16_rne_d(tn);
 }
 
-// ---------------------------------------------------------------------------
-// Gradient-norm clipping (opt-in): K11 measures, K9d applies.
-//
+// Split-K partials of one gradient, [>=S, stride]: element i is their sum
+// from 0.f in s order (k_reduce_arena).
+struct Arena { const float* ptr; long stride; int S; };
+
+__device__ __forceinline__ float arena_fold(const Arena& a, long i) {
+  float acc = 0.f;
+#pragma unroll 8
+  for (int s = 0; s < a.S; ++s) acc += a.ptr[(long)s * a.stride + i];
+  return acc;
+}
+
+// K9 with the step size from the host: the first Adam kernel, which no
+// engine steps through any more (adam_step_ is kept for tools and tests).
+// The one exception to adam_elem: as plain C++ this kernel was compiled
+// with b1*m, not (1-b1)*g, as the fused product of m, and with v as the
+// unfused sum of two rounded products.  Its results are kept, so it spells
+// out that sequence (profiles/adam_family.md).
+__global__ __launch_bounds__(256) void k_adam(
+    float* __restrict__ p, const float* __restrict__ g,
+    float* __restrict__ m, float* __restrict__ v, long n,
+    float b1, float b2, float step_size, float inv_sqrt_bc2, float eps) {
+#pragma clang fp contract(off)
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float gi = g[i];
+  const float mi = __fmaf_rn(b1, m[i], (1.f - b1) * gi);
+  const float vi = b2 * v[i] + ((1.f - b2) * gi) * gi;
+  m[i] = mi;
+  v[i] = vi;
+  p[i] -= step_size * mi / __fmaf_rn(sqrtf(vi), inv_sqrt_bc2, eps);
+}
+
+// K10 alone
+__global__ __launch_bounds__(256) void k_polyak(
+    float* __restrict__ t, const float* __restrict__ s, long n, float tau,
+    unsigned short* __restrict__ mir) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  polyak_elem(t, s, mir, i, tau);
+}
+
+// Graph-capturable Adam keeps {step, step_size, inv_sqrt_bc2} on-device so
+// a captured update's bias correction advances across hipGraph replays.
+// One launch advances the state of up to 4 optimizers (a null state is
+// skipped) and bumps the device RNG counter: the engine calls it once at
+// the top of seg2 and the steppers then skip their own prologs.
+__global__ void k_adam_prolog_many(long long* rng,
+                                   float* s0, float* s1, float* s2,
+                                   float* s3,
+                                   float lr0, float lr1, float lr2,
+                                   float lr3, float b1, float b2) {
+  if (rng != nullptr && threadIdx.x == 0) rng[0] += 1;
+  const int i = threadIdx.x;
+  float* sv[4] = {s0, s1, s2, s3};
+  const float lrv[4] = {lr0, lr1, lr2, lr3};
+  if (i >= 4 || sv[i] == nullptr) return;
+  float* st = sv[i];
+  const float step = st[0] + 1.f;
+  st[0] = step;
+  st[1] = lrv[i] / (1.f - __powf(b1, step));         // step_size
+  st[2] = 1.f / sqrtf(1.f - __powf(b2, step));       // inv_sqrt_bc2
+}
+
 // K11: sum of squares of up to three flat gradients, one launch.  Grid
 // (GN_SLOTS, ranges) is FIXED, so the summation order depends on n alone:
 // block b of a range owns elements b*256+tid + k*GN_SLOTS*256 (k ascending,
 // one fp32 accumulator per thread), then wave_sum64, then the four wave
 // partials left to right, written to slot [range][b].  GN_SLOTS = 256 blocks
 // per range: 64 of them left three quarters of the CUs idle and made the
-// flagship's critic fold 100 us long.  No atomics; the
-// launch boundary orders the slots for K9d.  Range 0 may come as a split-K
-// arena: it is folded from 0.f in s order (k_reduce_arena), the folded
-// value stored to the flat gradient and squared.
-// ---------------------------------------------------------------------------
+// flagship's critic fold 100 us long.  No atomics; the launch boundary
+// orders the slots for K9.  Range 0 may come as a split-K arena: the folded
+// value is stored to the flat gradient and squared.
 constexpr int GN_SLOTS = 256;
 
 __global__ __launch_bounds__(256) void k_grad_sumsq(
     float* g0, long n0, const float* g1, long n1, const float* g2, long n2,
-    const float* __restrict__ arena0, long stride0, int S0,
-    float* __restrict__ slots) {
+    const Arena arena0, float* __restrict__ slots) {
   __shared__ float s_w[4];
   const int r = blockIdx.y, tid = threadIdx.x;
   const float* g = r == 0 ? g0 : (r == 1 ? g1 : g2);
   const long n = r == 0 ? n0 : (r == 1 ? n1 : n2);
-  const bool fold = r == 0 && arena0 != nullptr;
+  const bool fold = r == 0 && arena0.ptr != nullptr;
   float acc = 0.f;
   for (long i = (long)blockIdx.x * 256 + tid; i < n;
        i += (long)GN_SLOTS * 256) {
     float x;
-    if (fold) {
-      float a = 0.f;
-#pragma unroll 8
-      for (int s = 0; s < S0; ++s) a += arena0[(long)s * stride0 + i];
-      g0[i] = a;
-      x = a;
-    } else {
-      x = g[i];
-    }
+    if (fold) g0[i] = x = arena_fold(arena0, i);
+    else x = g[i];
     acc += x * x;
   }
   acc = wave_sum64(acc);
@@ -2286,83 +2174,98 @@ __global__ __launch_bounds__(256) void k_grad_sumsq(
     slots[r * GN_SLOTS + blockIdx.x] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
 }
 
-// K9d: k_adam_multi_tail's index-range dispatch (<= 3 Adam groups + a
-// trailing Polyak range) on gradients that K11 measured.  Every block
-// re-sums each group's GN_SLOTS slots the same way (lane l adds slots l,
-// l+64, l+128, l+192 in that order, then wave_sum64), so all blocks derive
-// the same bits: s not finite -> the
-// group's threads leave p, m, v and the mirror alone; else
-// coef = min(1, c / (sqrtf(s) + 1e-6)) (torch clip_grad_norm_) and Adam runs
-// on coef * g — coef == 1.f leaves the arithmetic of k_adam_multi.  The flat
-// gradient is only read.  Block 0 publishes cs = {norm, coef, s} and bumps
-// the group's skip counter.
-__global__ __launch_bounds__(256) void k_adam_multi_clip(
-    float* p0, const float* g0, float* m0, float* v0, const float* st0, long n0,
-    float* p1, const float* g1, float* m1, float* v1, const float* st1, long n1,
-    float* p2, const float* g2, float* m2, float* v2, const float* st2, long n2,
-    float b1, float b2, float eps, unsigned short* mr0, unsigned short* mr1,
-    unsigned short* mr2, const float* __restrict__ slots,
-    float c0, float c1, float c2, float* cs0, float* cs1, float* cs2,
-    int* sk0, int* sk1, int* sk2,
-    float* __restrict__ pt, const float* __restrict__ psrc, long np,
-    float tau, unsigned short* __restrict__ pmir) {
+// Everything one k_adam_groups launch works on, passed by value.
+struct AdamGroup {
+  float* p; float* g; float* m; float* v; const float* st;   // st: state
+  unsigned short* mir; long n;
+};
+struct AdamTable {
+  AdamGroup grp[3];          // unused groups: n = 0
+  float b1, b2, eps;
+  Arena arena0;              // optional: group 0's gradient, folded here
+  float* pt; const float* psrc; unsigned short* pmir;   // optional trailing
+  long np; float tau;                                   // Polyak range
+  // CLIP only: K11's slots, thresholds, published {norm, coef, s}, counters
+  const float* slots; float c[3]; float* cs[3]; int* sk[3];
+};
+
+template <typename T>
+__device__ __forceinline__ T sel3(int k, T a0, T a1, T a2) {
+  return k == 0 ? a0 : (k == 1 ? a1 : a2);
+}
+
+// K9 (+K10): thread i takes one element of the concatenation of <= 3 Adam
+// groups and a trailing Polyak range (whose buffers must not be stepped by
+// this launch).  With arena0 set, group 0's gradient is folded from its
+// split-K partials and written back to the flat gradient for callers that
+// read .grad.
+//
+// CLIP: the gradients were measured by K11 (which also did the fold).
+// Every block re-sums each group's GN_SLOTS slots the same way (lane l adds
+// slots l, l+64, l+128, l+192 in that order, then wave_sum64), so all
+// blocks derive the same bits: s not finite -> the group's threads leave
+// p, m, v and the mirror alone; else coef = min(1, c / (sqrtf(s) + 1e-6))
+// (torch clip_grad_norm_) and Adam runs on coef * g.  The flat gradient is
+// only read.  Block 0 publishes cs = {norm, coef, s} and bumps the group's
+// skip counter.  LDS, the barrier and the atomic exist in this
+// instantiation alone, which is why CLIP is not a runtime flag.
+//
+// ONE: group 0 is all there is (the critic's step).  The group is then the
+// same for every lane, so its pointers and its state stay in scalar
+// registers; through the general dispatch that launch measured 0.1-0.3 us
+// longer (profiles/adam_family.md).
+template <bool CLIP, bool ONE>
+__global__ __launch_bounds__(256) void k_adam_groups(const AdamTable T) {
   __shared__ float s_coef[3];   // < 0: skip
-  const int tid = threadIdx.x, wv = tid >> 6;
-  if (wv < 3) {
-    const long nw = wv == 0 ? n0 : (wv == 1 ? n1 : n2);
-    if (nw > 0) {   // wave-uniform
-      const float* sl = slots + wv * GN_SLOTS + (tid & 63);
+  const int tid = threadIdx.x;
+  if constexpr (CLIP) {
+    const int wv = tid >> 6;
+    if (wv < 3 && sel3(wv, T.grp[0].n, T.grp[1].n, T.grp[2].n) > 0) {
+      const float* sl = T.slots + wv * GN_SLOTS + (tid & 63);   // wave-uniform
       const float s = wave_sum64(((sl[0] + sl[64]) + sl[128]) + sl[192]);
       if ((tid & 63) == 0) {
-        const float c = wv == 0 ? c0 : (wv == 1 ? c1 : c2);
+        const float c = sel3(wv, T.c[0], T.c[1], T.c[2]);
         const bool ok = fabsf(s) <= 3.402823466e+38f;   // false for NaN
         const float norm = sqrtf(s);
         const float coef = ok ? fminf(1.f, c / (norm + 1e-6f)) : -1.f;
         s_coef[wv] = coef;
         if (blockIdx.x == 0) {
-          float* cs = wv == 0 ? cs0 : (wv == 1 ? cs1 : cs2);
-          int* sk = wv == 0 ? sk0 : (wv == 1 ? sk1 : sk2);
+          float* cs = sel3(wv, T.cs[0], T.cs[1], T.cs[2]);
           cs[0] = norm; cs[1] = ok ? coef : 0.f; cs[2] = s;
           // groups of one launch may share a counter: the three bumps are
           // lanes of different waves, so go through the atomic unit
-          if (!ok) atomicAdd(sk, 1);
+          if (!ok) atomicAdd(sel3(wv, T.sk[0], T.sk[1], T.sk[2]), 1);
         }
       }
     }
+    __syncthreads();
   }
-  __syncthreads();
   long i = (long)blockIdx.x * blockDim.x + tid;
-  float* p; const float* g; float* m; float* v; const float* st;
-  unsigned short* mr; float coef;
-  if (i < n0) {
-    p = p0; g = g0; m = m0; v = v0; st = st0; mr = mr0; coef = s_coef[0];
+  AdamGroup G;
+  int k;
+  if constexpr (ONE) {
+    if (i >= T.grp[0].n) return;
+    G = T.grp[0]; k = 0;
   }
-  else if ((i -= n0) < n1) {
-    p = p1; g = g1; m = m1; v = v1; st = st1; mr = mr1; coef = s_coef[1];
-  }
-  else if ((i -= n1) < n2) {
-    p = p2; g = g2; m = m2; v = v2; st = st2; mr = mr2; coef = s_coef[2];
-  }
-  else if ((i -= n2) < np) {
-    const float tn = __fmaf_rn(1.f - tau, pt[i], tau * psrc[i]);
-    pt[i] = tn;
-    if (pmir != nullptr) pmir[i] = f32_bf16_rne_d(tn);
+  else if (i < T.grp[0].n) { G = T.grp[0]; k = 0; }
+  else if ((i -= T.grp[0].n) < T.grp[1].n) { G = T.grp[1]; k = 1; }
+  else if ((i -= T.grp[1].n) < T.grp[2].n) { G = T.grp[2]; k = 2; }
+  else {
+    if ((i -= T.grp[2].n) < T.np) polyak_elem(T.pt, T.psrc, T.pmir, i, T.tau);
     return;
   }
-  else return;
-  if (coef < 0.f) return;
-  // The Adam and Polyak expressions of k_adam_multi[_tail], with the
-  // roundings written out as the compiler contracts them there (which
-  // product fuses into the fma is its choice, and the extra multiply in
-  // front changes it): this kernel must give those kernels' bits.
-  const float gi = coef * g[i];
-  const float mi = __fmaf_rn(1.f - b1, gi, b1 * m[i]);
-  const float vi = __fmaf_rn(gi, (1.f - b2) * gi, b2 * v[i]);
-  m[i] = mi;
-  v[i] = vi;
-  const float pn = p[i] - st[1] * mi / __fmaf_rn(sqrtf(vi), st[2], eps);
-  p[i] = pn;
-  if (mr != nullptr) mr[i] = f32_bf16_rne_d(pn);
+  float gi;
+  if constexpr (CLIP) {
+    const float coef = s_coef[k];
+    if (coef < 0.f) return;
+    gi = coef * G.g[i];
+  } else {
+    if (k == 0 && T.arena0.ptr != nullptr)
+      G.g[i] = gi = arena_fold(T.arena0, i);
+    else
+      gi = G.g[i];
+  }
+  adam_elem(G.p, G.m, G.v, G.mir, i, gi, G.st[1], G.st[2], T.b1, T.b2, T.eps);
 }
 
 // ===========================================================================
@@ -3030,6 +2933,116 @@ static torch::Tensor squashed_gaussian_bwd2(
   return dhead;
 }
 
+// -- optimizer tail: the shared marshalling of the Adam/Polyak bindings ----
+using OptTensor = c10::optional<torch::Tensor>;
+
+static bool given(const OptTensor& t) {
+  return t.has_value() && t->defined() && t->numel() > 0;
+}
+
+static unsigned short* opt_mirror(const OptTensor& mir, long n) {
+  if (!given(mir)) return nullptr;
+  TORCH_CHECK(mir->is_cuda() && mir->numel() == n && mir->is_contiguous()
+              && mir->scalar_type() == torch::kBFloat16,
+              "mirror must be a bf16 HIP tensor of the group's numel");
+  return (unsigned short*)mir->data_ptr();
+}
+
+// optional [>=S, numel] split-K partials of the flat gradient g
+static Arena opt_arena(const OptTensor& arena, long S, const torch::Tensor& g) {
+  if (!given(arena)) return Arena{nullptr, 0, 0};
+  CHECK_IN(*arena); CHECK_IN(g);
+  TORCH_CHECK(arena->dim() == 2 && arena->is_contiguous() && g.is_contiguous()
+              && arena->size(1) == g.numel() && S >= 1 && S <= arena->size(0),
+              "arena must be [>=S, numel of the first gradient]");
+  return Arena{arena->data_ptr<float>(), g.numel(), (int)S};
+}
+
+// <= 3 Adam groups into a table; returns it with everything optional unset
+static AdamTable fill_groups(const std::vector<torch::Tensor>& ps,
+                             const std::vector<torch::Tensor>& gs,
+                             const std::vector<torch::Tensor>& ms,
+                             const std::vector<torch::Tensor>& vs,
+                             const std::vector<torch::Tensor>& states,
+                             const std::vector<torch::Tensor>& mirs,
+                             double b1, double b2, double eps) {
+  const size_t G = ps.size();
+  TORCH_CHECK(G >= 1 && G <= 3, "1..3 groups");
+  TORCH_CHECK(gs.size() == G && ms.size() == G && vs.size() == G
+              && states.size() == G && mirs.size() <= G,
+              "one entry per group");
+  AdamTable T{};
+  T.b1 = (float)b1; T.b2 = (float)b2; T.eps = (float)eps;
+  for (size_t k = 0; k < G; ++k) {
+    CHECK_IN(ps[k]); CHECK_IN(gs[k]); CHECK_IN(ms[k]); CHECK_IN(vs[k]);
+    CHECK_IN(states[k]);
+    const long n = ps[k].numel();
+    TORCH_CHECK(gs[k].numel() == n && ms[k].numel() == n
+                && vs[k].numel() == n && ps[k].is_contiguous()
+                && gs[k].is_contiguous() && ms[k].is_contiguous()
+                && vs[k].is_contiguous() && states[k].numel() >= 3,
+                "bad Adam group: p, g, m, v contiguous of one numel, "
+                "state = {step, step_size, inv_sqrt_bc2}");
+    T.grp[k] = AdamGroup{
+        ps[k].data_ptr<float>(), gs[k].data_ptr<float>(),
+        ms[k].data_ptr<float>(), vs[k].data_ptr<float>(),
+        states[k].data_ptr<float>(),
+        k < mirs.size() ? opt_mirror(mirs[k], n) : nullptr, n};
+  }
+  return T;
+}
+
+// optional Polyak range behind the Adam groups
+static void opt_polyak(AdamTable& T, const std::vector<torch::Tensor>& ps,
+                       const OptTensor& t, const OptTensor& s, double tau,
+                       const OptTensor& mir) {
+  if (!given(t)) return;
+  TORCH_CHECK(s.has_value(), "polyak source missing");
+  CHECK_IN(*t); CHECK_IN(*s);
+  TORCH_CHECK(s->numel() == t->numel() && t->is_contiguous()
+              && s->is_contiguous(), "polyak buffers must match");
+  for (const auto& p : ps)
+    TORCH_CHECK(s->data_ptr() != p.data_ptr() && t->data_ptr() != p.data_ptr(),
+                "polyak buffers must not be stepped in the same launch");
+  T.pt = t->data_ptr<float>();
+  T.psrc = s->data_ptr<float>();
+  T.np = t->numel();
+  T.tau = (float)tau;
+  T.pmir = opt_mirror(mir, T.np);
+}
+
+template <bool CLIP>
+static void launch_groups(const AdamTable& T) {
+  const long total = T.grp[0].n + T.grp[1].n + T.grp[2].n + T.np;
+  const dim3 grid((total + 255) / 256);
+  if (!CLIP && total == T.grp[0].n)
+    hipLaunchKernelGGL((k_adam_groups<false, true>), grid, dim3(256), 0,
+                       cur_stream(), T);
+  else
+    hipLaunchKernelGGL((k_adam_groups<CLIP, false>), grid, dim3(256), 0,
+                       cur_stream(), T);
+}
+
+static void adam_prolog_many(std::vector<torch::Tensor> states,
+                             std::vector<double> lrs, double b1, double b2,
+                             OptTensor rng) {
+  const size_t G = states.size();
+  TORCH_CHECK(G >= 1 && G <= 4 && lrs.size() == G, "1..4 states");
+  float* S[4] = {nullptr, nullptr, nullptr, nullptr};
+  float L[4] = {0.f, 0.f, 0.f, 0.f};
+  for (size_t g = 0; g < G; ++g) {
+    CHECK_IN(states[g]);
+    TORCH_CHECK(states[g].numel() >= 3,
+                "state = {step, step_size, inv_sqrt_bc2}");
+    S[g] = states[g].data_ptr<float>();
+    L[g] = (float)lrs[g];
+  }
+  long long* rng_p = given(rng) ? (long long*)rng->data_ptr<long>() : nullptr;
+  hipLaunchKernelGGL(k_adam_prolog_many, dim3(1), dim3(4), 0, cur_stream(),
+                     rng_p, S[0], S[1], S[2], S[3], L[0], L[1], L[2], L[3],
+                     (float)b1, (float)b2);
+}
+
 static void adam_step_(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                        torch::Tensor v, long step, double lr, double b1,
                        double b2, double eps) {
@@ -3046,71 +3059,21 @@ static void adam_step_(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                      (float)eps);
 }
 
+// one group; arena: optional [>=S, n] split-K partials folded into g
 static void adam_step_dev_(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                            torch::Tensor v, torch::Tensor state, double lr,
                            double b1, double b2, double eps,
-                           c10::optional<torch::Tensor> mir_opt,
-                           long skip_prolog = 0,
-                           c10::optional<torch::Tensor> arena = c10::nullopt,
-                           long S = 0) {
-  CHECK_IN(p); CHECK_IN(state);
-  TORCH_CHECK(state.numel() >= 3, "state = {step, step_size, inv_sqrt_bc2}");
-  const long n = p.numel();
-  // optional [>=S, n] split-K arena: the kernel folds it into g itself
-  const float* ap = nullptr;
-  if (arena.has_value() && arena->defined() && arena->numel() > 0) {
-    CHECK_IN(*arena); CHECK_IN(g);
-    TORCH_CHECK(arena->dim() == 2 && arena->is_contiguous()
-                && g.is_contiguous() && arena->size(1) == n
-                && g.numel() == n && S >= 1 && S <= arena->size(0),
-                "arena must be [>=S, numel]");
-    ap = arena->data_ptr<float>();
-  }
-  unsigned short* mp = nullptr;
-  if (mir_opt.has_value() && mir_opt->defined() && mir_opt->numel() > 0) {
-    TORCH_CHECK(mir_opt->numel() == n
-                && mir_opt->scalar_type() == torch::kBFloat16);
-    mp = (unsigned short*)mir_opt->data_ptr();
-  }
-  if (!skip_prolog)
-    hipLaunchKernelGGL(k_adam_prolog, dim3(1), dim3(1), 0, cur_stream(),
-                       state.data_ptr<float>(), (float)lr, (float)b1,
-                       (float)b2);
-  if (ap != nullptr) {
-    hipLaunchKernelGGL(k_adam_dev_arena, dim3((n + 255) / 256), dim3(256), 0,
-                       cur_stream(), p.data_ptr<float>(),
-                       g.data_ptr<float>(), m.data_ptr<float>(),
-                       v.data_ptr<float>(), state.data_ptr<float>(), n,
-                       (float)b1, (float)b2, (float)eps, mp, ap, n, (int)S);
-    return;
-  }
-  hipLaunchKernelGGL(k_adam_dev, dim3((n + 255) / 256), dim3(256), 0,
-                     cur_stream(), p.data_ptr<float>(), g.data_ptr<float>(),
-                     m.data_ptr<float>(), v.data_ptr<float>(),
-                     state.data_ptr<float>(), n, (float)b1, (float)b2,
-                     (float)eps, mp);
+                           OptTensor mir_opt, long skip_prolog = 0,
+                           OptTensor arena = c10::nullopt, long S = 0) {
+  AdamTable T = fill_groups({p}, {g}, {m}, {v}, {state},
+                            {given(mir_opt) ? *mir_opt : torch::Tensor()},
+                            b1, b2, eps);
+  T.arena0 = opt_arena(arena, S, g);
+  if (!skip_prolog) adam_prolog_many({state}, {lr}, b1, b2, c10::nullopt);
+  launch_groups<false>(T);
 }
 
-static void adam_prolog_many(std::vector<torch::Tensor> states,
-                             std::vector<double> lrs, double b1, double b2,
-                             c10::optional<torch::Tensor> rng) {
-  const size_t G = states.size();
-  TORCH_CHECK(G >= 1 && G <= 4 && lrs.size() == G, "1..4 states");
-  float* S[4] = {nullptr, nullptr, nullptr, nullptr};
-  double L[4] = {0, 0, 0, 0};
-  for (size_t g = 0; g < G; ++g) {
-    CHECK_IN(states[g]);
-    S[g] = states[g].data_ptr<float>();
-    L[g] = lrs[g];
-  }
-  long long* rng_p = (rng.has_value() && rng->numel() > 0)
-      ? (long long*)rng->data_ptr<long>() : nullptr;
-  hipLaunchKernelGGL(k_adam_prolog_many, dim3(1), dim3(4), 0, cur_stream(),
-                     rng_p, S[0], S[1], S[2], S[3], (float)L[0],
-                     (float)L[1], (float)L[2], (float)L[3], (float)b1,
-                     (float)b2);
-}
-
+// <= 3 groups [+ arena0 folded into gs[0]] [+ Polyak range]: [prolog,] K9
 static void adam_step_multi_(std::vector<torch::Tensor> ps,
                              std::vector<torch::Tensor> gs,
                              std::vector<torch::Tensor> ms,
@@ -3118,102 +3081,24 @@ static void adam_step_multi_(std::vector<torch::Tensor> ps,
                              std::vector<torch::Tensor> states,
                              std::vector<double> lrs, double b1, double b2,
                              double eps, std::vector<torch::Tensor> mirs,
-                             c10::optional<torch::Tensor> rng = c10::nullopt,
+                             OptTensor rng = c10::nullopt,
                              long skip_prolog = 0,
-                             c10::optional<torch::Tensor> arena0 = c10::nullopt,
-                             long S0 = 0,
-                             c10::optional<torch::Tensor> polyak_t = c10::nullopt,
-                             c10::optional<torch::Tensor> polyak_s = c10::nullopt,
+                             OptTensor arena0 = c10::nullopt, long S0 = 0,
+                             OptTensor polyak_t = c10::nullopt,
+                             OptTensor polyak_s = c10::nullopt,
                              double tau = 0.0,
-                             c10::optional<torch::Tensor> polyak_mir = c10::nullopt) {
-  const size_t G = ps.size();
-  TORCH_CHECK(G >= 1 && G <= 3, "1..3 groups");
-  float* P[3] = {nullptr, nullptr, nullptr};
-  const float* Gr[3] = {nullptr, nullptr, nullptr};
-  float* M[3] = {nullptr, nullptr, nullptr};
-  float* V[3] = {nullptr, nullptr, nullptr};
-  float* St[3] = {nullptr, nullptr, nullptr};
-  long N[3] = {0, 0, 0};
-  double LR[3] = {0, 0, 0};
-  unsigned short* MR[3] = {nullptr, nullptr, nullptr};
-  long total = 0;
-  for (size_t g = 0; g < G; ++g) {
-    CHECK_IN(ps[g]);
-    P[g] = ps[g].data_ptr<float>();
-    Gr[g] = gs[g].data_ptr<float>();
-    M[g] = ms[g].data_ptr<float>();
-    V[g] = vs[g].data_ptr<float>();
-    St[g] = states[g].data_ptr<float>();
-    N[g] = ps[g].numel();
-    LR[g] = lrs[g];
-    if (g < mirs.size() && mirs[g].defined() && mirs[g].numel() > 0) {
-      TORCH_CHECK(mirs[g].numel() == N[g]
-                  && mirs[g].scalar_type() == torch::kBFloat16);
-      MR[g] = (unsigned short*)mirs[g].data_ptr();
-    }
-    total += N[g];
-  }
-  long long* rng_p = (rng.has_value() && rng->numel() > 0)
-      ? (long long*)rng->data_ptr<long>() : nullptr;
-  if (!skip_prolog)
-    hipLaunchKernelGGL(k_adam_prolog3, dim3(1), dim3(3), 0, cur_stream(),
-                       rng_p, St[0], St[1], St[2], (float)LR[0],
-                       (float)LR[1], (float)LR[2], (float)b1, (float)b2);
-  // optional extras: split-K arena folded into group 0's gradient, and a
-  // Polyak range appended behind the Adam groups (k_adam_multi_tail)
-  const float* ap = nullptr;
-  if (arena0.has_value() && arena0->defined() && arena0->numel() > 0) {
-    CHECK_IN(*arena0); CHECK_IN(gs[0]);
-    TORCH_CHECK(arena0->dim() == 2 && arena0->is_contiguous()
-                && gs[0].is_contiguous() && arena0->size(1) == N[0]
-                && gs[0].numel() == N[0] && S0 >= 1
-                && S0 <= arena0->size(0), "arena0 must be [>=S0, numel0]");
-    ap = arena0->data_ptr<float>();
-  }
-  float* pt = nullptr; const float* psrc = nullptr; long np = 0;
-  unsigned short* pmir = nullptr;
-  if (polyak_t.has_value() && polyak_t->defined() && polyak_t->numel() > 0) {
-    TORCH_CHECK(polyak_s.has_value(), "polyak source missing");
-    CHECK_IN(*polyak_t); CHECK_IN(*polyak_s);
-    np = polyak_t->numel();
-    TORCH_CHECK(polyak_s->numel() == np && polyak_t->is_contiguous()
-                && polyak_s->is_contiguous(), "polyak buffers must match");
-    for (size_t g = 0; g < G; ++g)
-      TORCH_CHECK(polyak_s->data_ptr() != ps[g].data_ptr()
-                  && polyak_t->data_ptr() != ps[g].data_ptr(),
-                  "polyak buffers must not be stepped in the same launch");
-    pt = polyak_t->data_ptr<float>();
-    psrc = polyak_s->data_ptr<float>();
-    if (polyak_mir.has_value() && polyak_mir->defined()
-        && polyak_mir->numel() > 0) {
-      TORCH_CHECK(polyak_mir->numel() == np
-                  && polyak_mir->scalar_type() == torch::kBFloat16);
-      pmir = (unsigned short*)polyak_mir->data_ptr();
-    }
-  }
-  if (ap != nullptr || pt != nullptr) {
-    hipLaunchKernelGGL(k_adam_multi_tail, dim3((total + np + 255) / 256),
-                       dim3(256), 0, cur_stream(),
-                       P[0], gs[0].data_ptr<float>(), M[0], V[0], St[0], N[0],
-                       P[1], Gr[1], M[1], V[1], St[1], N[1],
-                       P[2], Gr[2], M[2], V[2], St[2], N[2],
-                       (float)b1, (float)b2, (float)eps, MR[0], MR[1], MR[2],
-                       ap, N[0], (int)S0, pt, psrc, np, (float)tau, pmir);
-    return;
-  }
-  hipLaunchKernelGGL(k_adam_multi, dim3((total + 255) / 256), dim3(256), 0,
-                     cur_stream(),
-                     P[0], Gr[0], M[0], V[0], St[0], N[0],
-                     P[1], Gr[1], M[1], V[1], St[1], N[1],
-                     P[2], Gr[2], M[2], V[2], St[2], N[2],
-                     (float)b1, (float)b2, (float)eps, MR[0], MR[1], MR[2]);
+                             OptTensor polyak_mir = c10::nullopt) {
+  AdamTable T = fill_groups(ps, gs, ms, vs, states, mirs, b1, b2, eps);
+  T.arena0 = opt_arena(arena0, S0, gs[0]);
+  opt_polyak(T, ps, polyak_t, polyak_s, tau, polyak_mir);
+  if (!skip_prolog) adam_prolog_many(states, lrs, b1, b2, rng);
+  launch_groups<false>(T);
 }
 
 // K11 alone: slots[r*GN_SLOTS + b] for r < gs.size(); arena0 as in
 // adam_step_multi_ (folded into gs[0], which is then written).
 static void grad_sumsq_(std::vector<torch::Tensor> gs, torch::Tensor slots,
-                        c10::optional<torch::Tensor> arena0 = c10::nullopt,
-                        long S0 = 0) {
+                        OptTensor arena0 = c10::nullopt, long S0 = 0) {
   const size_t G = gs.size();
   TORCH_CHECK(G >= 1 && G <= 3, "1..3 ranges");
   CHECK_IN(slots);
@@ -3227,22 +3112,12 @@ static void grad_sumsq_(std::vector<torch::Tensor> gs, torch::Tensor slots,
     Gp[g] = gs[g].data_ptr<float>();
     N[g] = gs[g].numel();
   }
-  const float* ap = nullptr;
-  long stride = 0;
-  if (arena0.has_value() && arena0->defined() && arena0->numel() > 0) {
-    CHECK_IN(*arena0);
-    TORCH_CHECK(arena0->dim() == 2 && arena0->is_contiguous()
-                && arena0->size(1) == N[0] && S0 >= 1
-                && S0 <= arena0->size(0), "arena0 must be [>=S0, numel0]");
-    ap = arena0->data_ptr<float>();
-    stride = N[0];
-  }
   hipLaunchKernelGGL(k_grad_sumsq, dim3(GN_SLOTS, (unsigned)G), dim3(256), 0,
                      cur_stream(), Gp[0], N[0], Gp[1], N[1], Gp[2], N[2],
-                     ap, stride, (int)S0, slots.data_ptr<float>());
+                     opt_arena(arena0, S0, gs[0]), slots.data_ptr<float>());
 }
 
-// adam_step_multi_ with gradient-norm clipping: [prolog,] K11, K9d.
+// adam_step_multi_ with gradient-norm clipping: [prolog,] K11, K9<CLIP>.
 // maxn[g]: the group's threshold (inf = guard only); clip_states[g]: fp32
 // {norm, coef, s}; skips[g]: int32 counter (groups may share one).
 static void adam_step_clip_(std::vector<torch::Tensor> ps,
@@ -3255,111 +3130,43 @@ static void adam_step_clip_(std::vector<torch::Tensor> ps,
                             torch::Tensor slots, std::vector<double> maxn,
                             std::vector<torch::Tensor> clip_states,
                             std::vector<torch::Tensor> skips,
-                            c10::optional<torch::Tensor> rng = c10::nullopt,
+                            OptTensor rng = c10::nullopt,
                             long skip_prolog = 0,
-                            c10::optional<torch::Tensor> arena0 = c10::nullopt,
-                            long S0 = 0,
-                            c10::optional<torch::Tensor> polyak_t = c10::nullopt,
-                            c10::optional<torch::Tensor> polyak_s = c10::nullopt,
+                            OptTensor arena0 = c10::nullopt, long S0 = 0,
+                            OptTensor polyak_t = c10::nullopt,
+                            OptTensor polyak_s = c10::nullopt,
                             double tau = 0.0,
-                            c10::optional<torch::Tensor> polyak_mir = c10::nullopt) {
+                            OptTensor polyak_mir = c10::nullopt) {
+  AdamTable T = fill_groups(ps, gs, ms, vs, states, mirs, b1, b2, eps);
   const size_t G = ps.size();
-  TORCH_CHECK(G >= 1 && G <= 3, "1..3 groups");
-  TORCH_CHECK(gs.size() == G && ms.size() == G && vs.size() == G
-              && states.size() == G && lrs.size() == G && maxn.size() == G
-              && clip_states.size() == G && skips.size() == G,
-              "one entry per group");
-  float* P[3] = {nullptr, nullptr, nullptr};
-  const float* Gr[3] = {nullptr, nullptr, nullptr};
-  float* M[3] = {nullptr, nullptr, nullptr};
-  float* V[3] = {nullptr, nullptr, nullptr};
-  float* St[3] = {nullptr, nullptr, nullptr};
-  float* CS[3] = {nullptr, nullptr, nullptr};
-  int* SK[3] = {nullptr, nullptr, nullptr};
-  float C[3] = {0.f, 0.f, 0.f};
-  long N[3] = {0, 0, 0};
-  double LR[3] = {0, 0, 0};
-  unsigned short* MR[3] = {nullptr, nullptr, nullptr};
-  long total = 0;
-  for (size_t g = 0; g < G; ++g) {
-    CHECK_IN(ps[g]); CHECK_IN(gs[g]); CHECK_IN(ms[g]); CHECK_IN(vs[g]);
-    CHECK_IN(states[g]); CHECK_IN(clip_states[g]);
-    N[g] = ps[g].numel();
-    TORCH_CHECK(gs[g].numel() == N[g] && ms[g].numel() == N[g]
-                && vs[g].numel() == N[g] && gs[g].is_contiguous()
-                && states[g].numel() >= 3 && clip_states[g].numel() >= 3
-                && skips[g].is_cuda() && skips[g].numel() >= 1
-                && skips[g].scalar_type() == torch::kInt32
-                && maxn[g] > 0.0, "bad clipped Adam group");
-    P[g] = ps[g].data_ptr<float>();
-    Gr[g] = gs[g].data_ptr<float>();
-    M[g] = ms[g].data_ptr<float>();
-    V[g] = vs[g].data_ptr<float>();
-    St[g] = states[g].data_ptr<float>();
-    CS[g] = clip_states[g].data_ptr<float>();
-    SK[g] = skips[g].data_ptr<int>();
-    C[g] = (float)maxn[g];
-    LR[g] = lrs[g];
-    if (g < mirs.size() && mirs[g].defined() && mirs[g].numel() > 0) {
-      TORCH_CHECK(mirs[g].numel() == N[g]
-                  && mirs[g].scalar_type() == torch::kBFloat16);
-      MR[g] = (unsigned short*)mirs[g].data_ptr();
-    }
-    total += N[g];
+  TORCH_CHECK(maxn.size() == G && clip_states.size() == G
+              && skips.size() == G, "one entry per group");
+  for (size_t k = 0; k < G; ++k) {
+    CHECK_IN(clip_states[k]);
+    TORCH_CHECK(clip_states[k].numel() >= 3 && skips[k].is_cuda()
+                && skips[k].numel() >= 1
+                && skips[k].scalar_type() == torch::kInt32
+                && maxn[k] > 0.0, "bad clipped Adam group");
+    T.c[k] = (float)maxn[k];
+    T.cs[k] = clip_states[k].data_ptr<float>();
+    T.sk[k] = skips[k].data_ptr<int>();
   }
-  long long* rng_p = (rng.has_value() && rng->numel() > 0)
-      ? (long long*)rng->data_ptr<long>() : nullptr;
-  if (!skip_prolog)
-    hipLaunchKernelGGL(k_adam_prolog3, dim3(1), dim3(3), 0, cur_stream(),
-                       rng_p, St[0], St[1], St[2], (float)LR[0],
-                       (float)LR[1], (float)LR[2], (float)b1, (float)b2);
-  grad_sumsq_(gs, slots, arena0, S0);
-  float* pt = nullptr; const float* psrc = nullptr; long np = 0;
-  unsigned short* pmir = nullptr;
-  if (polyak_t.has_value() && polyak_t->defined() && polyak_t->numel() > 0) {
-    TORCH_CHECK(polyak_s.has_value(), "polyak source missing");
-    CHECK_IN(*polyak_t); CHECK_IN(*polyak_s);
-    np = polyak_t->numel();
-    TORCH_CHECK(polyak_s->numel() == np && polyak_t->is_contiguous()
-                && polyak_s->is_contiguous(), "polyak buffers must match");
-    for (size_t g = 0; g < G; ++g)
-      TORCH_CHECK(polyak_s->data_ptr() != ps[g].data_ptr()
-                  && polyak_t->data_ptr() != ps[g].data_ptr(),
-                  "polyak buffers must not be stepped in the same launch");
-    pt = polyak_t->data_ptr<float>();
-    psrc = polyak_s->data_ptr<float>();
-    if (polyak_mir.has_value() && polyak_mir->defined()
-        && polyak_mir->numel() > 0) {
-      TORCH_CHECK(polyak_mir->numel() == np
-                  && polyak_mir->scalar_type() == torch::kBFloat16);
-      pmir = (unsigned short*)polyak_mir->data_ptr();
-    }
-  }
-  hipLaunchKernelGGL(k_adam_multi_clip, dim3((total + np + 255) / 256),
-                     dim3(256), 0, cur_stream(),
-                     P[0], Gr[0], M[0], V[0], St[0], N[0],
-                     P[1], Gr[1], M[1], V[1], St[1], N[1],
-                     P[2], Gr[2], M[2], V[2], St[2], N[2],
-                     (float)b1, (float)b2, (float)eps, MR[0], MR[1], MR[2],
-                     slots.data_ptr<float>(), C[0], C[1], C[2],
-                     CS[0], CS[1], CS[2], SK[0], SK[1], SK[2],
-                     pt, psrc, np, (float)tau, pmir);
+  opt_polyak(T, ps, polyak_t, polyak_s, tau, polyak_mir);
+  if (!skip_prolog) adam_prolog_many(states, lrs, b1, b2, rng);
+  grad_sumsq_(gs, slots, arena0, S0);   // checks slots; folds arena0
+  T.slots = slots.data_ptr<float>();
+  launch_groups<true>(T);
 }
 
 static void polyak_(torch::Tensor t, torch::Tensor s, double tau,
-                    c10::optional<torch::Tensor> mir_opt) {
-  CHECK_IN(t);
+                    OptTensor mir_opt) {
+  CHECK_IN(t); CHECK_IN(s);
   const long n = t.numel();
-  TORCH_CHECK(s.numel() == n, "polyak buffers must match");
-  unsigned short* mp = nullptr;
-  if (mir_opt.has_value() && mir_opt->defined() && mir_opt->numel() > 0) {
-    TORCH_CHECK(mir_opt->numel() == n
-                && mir_opt->scalar_type() == torch::kBFloat16);
-    mp = (unsigned short*)mir_opt->data_ptr();
-  }
+  TORCH_CHECK(s.numel() == n && t.is_contiguous() && s.is_contiguous(),
+              "polyak buffers must match");
   hipLaunchKernelGGL(k_polyak, dim3((n + 255) / 256), dim3(256), 0,
                      cur_stream(), t.data_ptr<float>(), s.data_ptr<float>(),
-                     n, (float)tau, mp);
+                     n, (float)tau, opt_mirror(mir_opt, n));
 }
 
 // -- prioritized replay ------------------------------------------------------

@@ -95,25 +95,59 @@ class FlatParams:
         return self.flat_data[off:off + p.numel()].view_as(p.data)
 
 
-def flat_polyak_(target: FlatParams, source: FlatParams, tau: float,
+@torch.no_grad()
+def polyak_flat_(t: torch.Tensor, s: torch.Tensor, tau: float,
                  mirror: Optional[torch.Tensor] = None) -> None:
-    """target <- tau*source + (1-tau)*target over whole flat buffers; with
-    ``mirror`` set, the target's bf16 compute mirror is refreshed in the
-    same kernel (no separate cast launch).
-
-    Requires identical parameter ordering (enforced by matching numel).
-    """
-    assert target.numel == source.numel
-    t, s = target.flat_data, source.flat_data
+    """t <- tau*s + (1-tau)*t over two flat fp32 tensors (whole buffers or
+    matching slices); with ``mirror`` set, t's bf16 compute mirror is
+    refreshed in the same kernel (no separate cast launch)."""
     if t.is_cuda and native_enabled() and has_native():
-        if mirror is not None:
-            native().polyak_(t, s, float(tau), mirror)
-        else:
-            native().polyak_(t, s, float(tau))
+        native().polyak_(t, s, float(tau), mirror)
         return
     t.mul_(1.0 - tau).add_(s, alpha=tau)
     if mirror is not None:
         mirror.copy_(t)
+
+
+def flat_polyak_(target: FlatParams, source: FlatParams, tau: float,
+                 mirror: Optional[torch.Tensor] = None) -> None:
+    """:func:`polyak_flat_` over whole groups.  Requires identical
+    parameter ordering (enforced by matching numel)."""
+    assert target.numel == source.numel
+    polyak_flat_(target.flat_data, source.flat_data, tau, mirror)
+
+
+def _native_step(opts: List["FusedAdam"], rng_bump, pre_prologed, arena0,
+                 polyak) -> None:
+    """The one caller of the HIP steppers: <= 3 optimizers with device
+    state and the same betas/eps, see :meth:`FusedAdam.step_many`."""
+    clip = opts[0].max_grad_norm is not None
+    assert all((o.max_grad_norm is not None) == clip for o in opts), \
+        "clipping is per launch: set it on every optimizer"
+    args = [
+        [o.group.flat_data for o in opts],
+        [o.group.flat_grad for o in opts],
+        [o.exp_avg for o in opts],
+        [o.exp_avg_sq for o in opts],
+        [o._dev_state for o in opts],
+        [o.lr for o in opts],
+        opts[0].betas[0], opts[0].betas[1], opts[0].eps,
+        [o.bf16_mirror if o.bf16_mirror is not None
+         else torch.Tensor() for o in opts]]
+    if clip:
+        args += [opts[0]._clip_slots,
+                 [o.max_grad_norm for o in opts],
+                 [o._clip_state for o in opts],
+                 [o._skips for o in opts]]
+    args += [rng_bump, 1 if pre_prologed else 0,
+             arena0[0] if arena0 is not None else None,
+             int(arena0[1]) if arena0 is not None else 0]
+    if polyak is not None:
+        target, source, tau, mirror = polyak
+        assert target.numel == source.numel
+        args += [target.flat_data, source.flat_data, float(tau), mirror]
+    ext = native()
+    (ext.adam_step_clip_ if clip else ext.adam_step_multi_)(*args)
 
 
 class FusedAdam:
@@ -201,31 +235,6 @@ class FusedAdam:
         """Cumulative number of skipped steps (0-d int32 view)."""
         return None if self._skips is None else self._skips[0]
 
-    def _step_clip_native(self, opts, rng_bump, pre_prologed, arena0,
-                          polyak) -> None:
-        args = [
-            [o.group.flat_data for o in opts],
-            [o.group.flat_grad for o in opts],
-            [o.exp_avg for o in opts],
-            [o.exp_avg_sq for o in opts],
-            [o._dev_state for o in opts],
-            [o.lr for o in opts],
-            self.betas[0], self.betas[1], self.eps,
-            [o.bf16_mirror if o.bf16_mirror is not None
-             else torch.Tensor() for o in opts],
-            self._clip_slots,
-            [o.max_grad_norm for o in opts],
-            [o._clip_state for o in opts],
-            [o._skips for o in opts],
-            rng_bump, 1 if pre_prologed else 0,
-            arena0[0] if arena0 is not None else None,
-            int(arena0[1]) if arena0 is not None else 0]
-        if polyak is not None:
-            target, source, tau, mirror = polyak
-            assert target.numel == source.numel
-            args += [target.flat_data, source.flat_data, float(tau), mirror]
-        native().adam_step_clip_(*args)
-
     @property
     def step_count(self) -> int:
         if self._dev_state is not None:
@@ -251,21 +260,7 @@ class FusedAdam:
         m, v = self.exp_avg, self.exp_avg_sq
         b1, b2 = self.betas
         if self._dev_state is not None:
-            if self.max_grad_norm is not None:
-                self._step_clip_native([self], None, pre_prologed, arena,
-                                       None)
-                return
-            if arena is not None:
-                native().adam_step_dev_(p, g, m, v, self._dev_state,
-                                        self.lr, b1, b2, self.eps,
-                                        self.bf16_mirror,
-                                        1 if pre_prologed else 0,
-                                        arena[0], int(arena[1]))
-                return
-            native().adam_step_dev_(p, g, m, v, self._dev_state,
-                                    self.lr, b1, b2, self.eps,
-                                    self.bf16_mirror,
-                                    1 if pre_prologed else 0)
+            _native_step([self], None, pre_prologed, arena, None)
             return
         if arena is not None:
             g.zero_()
@@ -312,32 +307,7 @@ class FusedAdam:
                 and all(o._dev_state is not None for o in live)
                 and all(o.betas == live[0].betas and o.eps == live[0].eps
                         for o in live)):
-            if any(o.max_grad_norm is not None for o in live):
-                assert all(o.max_grad_norm is not None for o in live), \
-                    "clipping is per launch: set it on every optimizer"
-                live[0]._step_clip_native(live, rng_bump, pre_prologed,
-                                          arena0, polyak)
-                return
-            args = [
-                [o.group.flat_data for o in live],
-                [o.group.flat_grad for o in live],
-                [o.exp_avg for o in live],
-                [o.exp_avg_sq for o in live],
-                [o._dev_state for o in live],
-                [o.lr for o in live],
-                live[0].betas[0], live[0].betas[1], live[0].eps,
-                [o.bf16_mirror if o.bf16_mirror is not None
-                 else torch.Tensor() for o in live],
-                rng_bump, 1 if pre_prologed else 0]
-            if arena0 is not None or polyak is not None:
-                args += [arena0[0] if arena0 is not None else None,
-                         int(arena0[1]) if arena0 is not None else 0]
-                if polyak is not None:
-                    target, source, tau, mirror = polyak
-                    assert target.numel == source.numel
-                    args += [target.flat_data, source.flat_data, float(tau),
-                             mirror]
-            native().adam_step_multi_(*args)
+            _native_step(live, rng_bump, pre_prologed, arena0, polyak)
             return
         # unfused fallback: same effects, one launch each
         if rng_bump is not None and not pre_prologed:
