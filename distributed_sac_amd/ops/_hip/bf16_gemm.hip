@@ -42,10 +42,9 @@ static inline hipStream_t cur_stream2() {
 }
 
 __device__ __forceinline__ u16 f32_to_bf16_rne(float f) {
-  union { float f; unsigned u; } v{f};
-  unsigned u = v.u;
-  u += 0x7FFFu + ((u >> 16) & 1u);   // round-to-nearest-even
-  return (u16)(u >> 16);
+  // native v_cvt_pk_bf16_f32: round to nearest even, and a NaN stays a
+  // NaN (the integer rounding add carried some into Inf or zero)
+  return __builtin_bit_cast(u16, (__bf16)f);
 }
 
 __global__ __launch_bounds__(256) void k_cast_f32_bf16(

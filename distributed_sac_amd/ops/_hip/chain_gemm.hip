@@ -62,10 +62,9 @@ static inline hipStream_t cur_stream3() {
 }
 
 __device__ __forceinline__ u16 f32_to_bf16_rne3(float f) {
-  union { float f; unsigned u; } v{f};
-  unsigned u = v.u;
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (u16)(u >> 16);
+  // native v_cvt_pk_bf16_f32: round to nearest even, and a NaN stays a
+  // NaN (the integer rounding add carried some into Inf or zero)
+  return __builtin_bit_cast(u16, (__bf16)f);
 }
 
 struct ChainFwdDesc {

@@ -822,10 +822,9 @@ __global__ __launch_bounds__(256) void k_critic_loss_bwd2(
   const float w_raw = use_w ? smw[t_i] : 1.f;
   const float coeff = (use_w ? w_raw / saved[2] : 1.f) / (float)B;
   auto cvt = [](float f) -> unsigned short {
-    union { float f; unsigned u; } v{f};
-    unsigned u = v.u;
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
+    // native v_cvt_pk_bf16_f32: round to nearest even, and a NaN stays a
+    // NaN (the integer rounding add carried some into Inf or zero)
+    return __builtin_bit_cast(unsigned short, (__bf16)f);
   };
   dq[i] = cvt(coeff * -2.f * (y[i] - q1[i]));
   dq[B + i] = cvt(coeff * -2.f * (y[i] - q2[i]));
@@ -1165,10 +1164,9 @@ __global__ __launch_bounds__(256) void k_actor_alpha_loss_bwd2(
     const float coeff = (use_w ? w_raw / saved[1] : 1.f) / (float)B;
     const bool first = aq1[i] <= aq2[i];
     auto cvt = [](float f) -> unsigned short {
-      union { float f; unsigned u; } v{f};
-      unsigned u = v.u;
-      u += 0x7FFFu + ((u >> 16) & 1u);
-      return (unsigned short)(u >> 16);
+      // native v_cvt_pk_bf16_f32: round to nearest even, and a NaN stays a
+      // NaN (the integer rounding add carried some into Inf or zero)
+      return __builtin_bit_cast(unsigned short, (__bf16)f);
     };
     daq[i] = cvt(first ? coeff * -1.f : 0.f);
     daq[B + i] = cvt(first ? 0.f : coeff * -1.f);
@@ -1214,10 +1212,9 @@ __global__ __launch_bounds__(256) void k_squash_bwd2(
   if (i >= B) return;
   const float g = gl[i];
   auto cvt = [](float f) -> unsigned short {
-    union { float f; unsigned u; } v{f};
-    unsigned u = v.u;
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
+    // native v_cvt_pk_bf16_f32: round to nearest even, and a NaN stays a
+    // NaN (the integer rounding add carried some into Inf or zero)
+    return __builtin_bit_cast(unsigned short, (__bf16)f);
   };
   for (int a = 0; a < A; ++a) {
     const long idx = (long)i * A + a;
@@ -1239,10 +1236,9 @@ __global__ __launch_bounds__(256) void k_squash_bwd2(
 }
 
 __device__ __forceinline__ unsigned short f32_bf16_rne_d(float f) {
-  union { float f; unsigned u; } v{f};
-  unsigned u = v.u;
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
+  // native v_cvt_pk_bf16_f32: round to nearest even, and a NaN stays a
+  // NaN (the integer rounding add carried some into Inf or zero)
+  return __builtin_bit_cast(unsigned short, (__bf16)f);
 }
 
 // ---------------------------------------------------------------------------

@@ -563,3 +563,111 @@ def grad_clip_coef(g: torch.Tensor, max_norm: float):
     coef = torch.where(ok, (c / (norm + tiny)).clamp(max=1.0),
                        torch.zeros_like(norm))
     return s, norm, coef, ok
+
+
+# ---------------------------------------------------------------------------
+# bf16 MFMA GEMM oracle (docs/KERNELS.md "Numerics").  Every GEMM kernel
+# takes bf16 operands (exact in float64), forms exact products, adds them in
+# fp32 in an order the hardware does not specify, and rounds once at the
+# end.  So the check is an inequality: with ``n`` accumulated terms and
+# ``mag = sum |a| |w| (+ |bias|)``, any order of n fp32 additions stays
+# within ``(n + 2) * 2^-23 * mag`` of the exact sum — one whole ulp per
+# addition, so an adder that truncates satisfies it too — plus a floor for
+# a flushed denormal.  A bf16 output adds its own rounding, unit roundoff
+# 2^-8.  Feeding each layer the kernel's own saved bf16 input ("teacher
+# forcing") makes every layer one such GEMM with exactly known operands.
+# ---------------------------------------------------------------------------
+
+GEMM_ULP = 2.0 ** -23       # one fp32 ulp (relative) per addition
+GEMM_FLOOR = 2.0 ** -100    # a flushed denormal
+BF16_ROUNDOFF = 2.0 ** -8   # unit roundoff of bf16 (8 significant bits)
+
+
+@torch.no_grad()
+def gemm_oracle(a: torch.Tensor, w: torch.Tensor,
+                bias: Optional[torch.Tensor] = None, relu: bool = False,
+                mask: Optional[torch.Tensor] = None,
+                n: Optional[int] = None):
+    """``(ref, tol)`` in float64 of ``a [..., M, K] @ w [..., N, K]^T``
+    (+ ``bias [..., N]``), ReLU and ``mask`` (False = forced to exactly 0)
+    applied in float64.  ``n`` is the number of accumulated terms (default
+    K; rows plus partials for a split-K sum, every term for a sum over
+    groups).  ``tol = (n + 2) * 2^-23 * mag + 2^-100``; where the mask
+    forces a zero, ``tol`` is 0."""
+    a64, w64 = a.double(), w.double()
+    ref = a64 @ w64.transpose(-1, -2)
+    mag = a64.abs() @ w64.abs().transpose(-1, -2)
+    if bias is not None:
+        b64 = bias.double().unsqueeze(-2)
+        ref = ref + b64
+        mag = mag + b64.abs()
+    if n is None:
+        n = a.shape[-1]
+    tol = (n + 2) * GEMM_ULP * mag + GEMM_FLOOR
+    if relu:
+        ref = ref.clamp(min=0.0)     # |relu(x) - relu(y)| <= |x - y|
+    if mask is not None:
+        ref = torch.where(mask, ref, torch.zeros_like(ref))
+        tol = torch.where(mask, tol, torch.zeros_like(tol))
+    return ref, tol
+
+
+@torch.no_grad()
+def gemm_bound_ratio(out: torch.Tensor, ref: torch.Tensor,
+                     tol: torch.Tensor) -> torch.Tensor:
+    """Elementwise ``err / bound`` of a kernel output against
+    :func:`gemm_oracle`: the bound is ``tol`` for an fp32 output and
+    ``tol + 2^-8 (|ref| + tol)`` for a bf16 one.  An element within its
+    bound yields a ratio in [0, 1]; one outside it, or not finite, yields
+    ``inf``."""
+    if out.dtype == torch.bfloat16:
+        bound = tol + BF16_ROUNDOFF * (ref.abs() + tol)
+    elif out.dtype == torch.float32:
+        bound = tol
+    else:
+        raise TypeError(f"kernel outputs are fp32 or bf16, got {out.dtype}")
+    if out.shape != ref.shape:
+        raise ValueError(f"shape {tuple(out.shape)} != {tuple(ref.shape)}")
+    err = (out.double() - ref).abs()
+    ok = err <= bound                # False for NaN
+    ratio = torch.where(bound > 0, err / bound, torch.zeros_like(err))
+    return torch.where(ok, ratio, torch.full_like(err, float("inf")))
+
+
+def pack_frag_ref(w: torch.Tensor, G: int, dx: bool = False) -> torch.Tensor:
+    """The fragment-packed mirror of ``w [G, N, K]`` (flattened groups
+    allowed) by index arithmetic:
+    ``P[((g NT + t) KS + ks) 64 + l][j] = W[g][t 16 + (l & 15)]
+    [ks 32 + (l >> 4) 8 + j]``, zero out of range; ``dx`` packs W
+    transposed.  Returns the flat ``[G * NT * KS * 512]`` tensor."""
+    K = w.shape[-1]
+    w3 = w.reshape(G, -1, K)
+    if dx:
+        w3 = w3.transpose(1, 2)
+    rows, cols = w3.shape[1], w3.shape[2]
+    NT, KS = (rows + 15) // 16, (cols + 31) // 32
+    padded = torch.zeros(G, NT * 16, KS * 32, dtype=w.dtype, device=w.device)
+    padded[:, :rows, :cols] = w3
+    dev = w.device
+    lane = torch.arange(64, device=dev)
+    r = torch.arange(NT, device=dev)[:, None, None, None] * 16 \
+        + (lane & 15)[None, None, :, None]
+    c = torch.arange(KS, device=dev)[None, :, None, None] * 32 \
+        + ((lane >> 4) * 8)[None, None, :, None] \
+        + torch.arange(8, device=dev)[None, None, None, :]
+    r, c = torch.broadcast_tensors(r, c)
+    return padded[:, r, c].reshape(-1)
+
+
+def f32_to_bf16_bits(u: torch.Tensor) -> torch.Tensor:
+    """The kernels' fp32 -> bf16 conversion on bit patterns (int64 tensors
+    holding 32-bit words; returns 16-bit words): round to nearest, ties to
+    even — add ``0x7FFF + (bit 16)``, drop the low half.  A NaN must stay a
+    NaN; that add would carry one with a small mantissa into Inf or zero.
+    Here it gets its quiet bit set and keeps its sign; the kernels use the
+    native conversion instruction, which picks its own NaN payload, so only
+    the non-NaN words are comparable bit for bit."""
+    u = u & 0xFFFFFFFF
+    is_nan = (u & 0x7FFFFFFF) > 0x7F800000
+    rne = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFFFFFF
+    return torch.where(is_nan, u | 0x00400000, rne) >> 16
