@@ -581,6 +581,12 @@ __global__ __launch_bounds__(256) void k_replay_ingest(
 // K4: fused tanh-squashed Gaussian sample + log-prob (fwd + bwd).
 // One thread per batch row; A = action_dim <= 32.
 // ---------------------------------------------------------------------------
+// d clamp(x, -20, 2) / dx for the backward: 1 inside, 0 outside, and the
+// NaN itself for a NaN x, so that it reaches the gradient
+__device__ __forceinline__ float dsac_clamp_mask(float raw) {
+  return (raw >= -20.f && raw <= 2.f) ? 1.f : (raw != raw ? raw : 0.f);
+}
+
 __global__ __launch_bounds__(256) void k_squash_fwd(
     const float* __restrict__ mu, const float* __restrict__ lsr,
     float* __restrict__ eps, float* __restrict__ act,
@@ -595,7 +601,10 @@ __global__ __launch_bounds__(256) void k_squash_fwd(
   float lp = 0.f;
   for (int a = 0; a < A; ++a) {
     const long idx = (long)i * A + a;
-    const float ls = fminf(fmaxf(lsr[(long)i * ls_ld + a], -20.f), 2.f);
+    // fminf/fmaxf return the other operand for a NaN: a NaN log-std must
+    // stay one (torch.clamp), or it leaves here as a finite logp
+    const float raw = lsr[(long)i * ls_ld + a];
+    const float ls = raw != raw ? raw : fminf(fmaxf(raw, -20.f), 2.f);
     const float s = __expf(ls);
     float e;
     if (rng != nullptr) {
@@ -639,7 +648,7 @@ __global__ __launch_bounds__(256) void k_squash_bwd(
     const float du = ga[idx] * k * omt2 + g * dlp_du;   // dL/du
     dmu[idx] = du;
     const float raw = lsr[idx];
-    const float mask = (raw >= -20.f && raw <= 2.f) ? 1.f : 0.f;
+    const float mask = dsac_clamp_mask(raw);
     dlsr[idx] = mask * (du * e * s - g);
   }
 }
@@ -1229,7 +1238,7 @@ __global__ __launch_bounds__(256) void k_squash_bwd2(
     const float gav = ga_twin ? ga[idx] + ga[(long)B * A + idx] : ga[idx];
     const float du = gav * k * omt2 + g * dlp_du;
     const float raw = lsr[(long)i * lsr_ld + a];
-    const float mask = (raw >= -20.f && raw <= 2.f) ? 1.f : 0.f;
+    const float mask = dsac_clamp_mask(raw);
     dhead[(long)i * 2 * A + a] = cvt(du);
     dhead[(long)i * 2 * A + A + a] = cvt(mask * (du * e * s - g));
   }

@@ -671,3 +671,210 @@ def f32_to_bf16_bits(u: torch.Tensor) -> torch.Tensor:
     is_nan = (u & 0x7FFFFFFF) > 0x7F800000
     rne = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFFFFFF
     return torch.where(is_nan, u | 0x00400000, rne) >> 16
+
+
+# ---------------------------------------------------------------------------
+# Squash (K4) and attention-pool (K3) oracles (docs/KERNELS.md "Numerics").
+# Float64 references computed from the kernels' exact fp32 / bf16 inputs,
+# each returned next to a per-element bound in units of u = 2^-24 (the fp32
+# unit roundoff), so a test reports err / bound as for the GEMMs.  The
+# bounds' structure follows the kernels' arithmetic; the only allowances
+# are those of the transcendental calls, in ulps: four times the worst
+# error (rounded up, at least 1) of the fp32 torch call against float64
+# over the test inputs (profiles/squash_reference.md) — the device's fast
+# variants are not specified that far.  The constants are the kernels'
+# fp32 constants widened, not the decimal values.
+# ---------------------------------------------------------------------------
+
+SQ_U = 2.0 ** -24
+SQ_E_EXP = 4
+SQ_E_LOG = 4
+SQ_E_TANH = 4
+SQ_E_COS = 4
+SQ_EPS6 = float(torch.tensor(1e-6, dtype=torch.float32))
+SQ_C = float(torch.tensor(0.9189385332046727, dtype=torch.float32))
+SQ_EPS_BOUND = 2.0 ** -20       # |e - e64| <= 2^-20 (r + 1)
+
+
+@torch.no_grad()
+def bound_ratio(out: torch.Tensor, ref: torch.Tensor,
+                tol: torch.Tensor) -> torch.Tensor:
+    """:func:`gemm_bound_ratio` that also accepts a NaN reference: there
+    the ratio is 0 if the output is a NaN too and ``inf`` if it is not."""
+    nan = torch.isnan(ref)
+    z = torch.zeros_like(ref)
+    r = gemm_bound_ratio(out, torch.where(nan, z, ref),
+                         torch.where(nan, z, tol))
+    hit = torch.where(torch.isnan(out.double()), z,
+                      torch.full_like(ref, float("inf")))
+    return torch.where(nan, hit, r)
+
+
+@torch.no_grad()
+def squash_eps_oracle(ctr, B: int, A: int):
+    """``(e, r)`` float64 ``[B, A]``: the Box-Muller draw of k_squash_fwd's
+    counter mode.  Element ``idx = i A + a`` hashes
+    ``h1 = sm64(c 0x100000001 + 2 idx + 1)``, ``h2 = sm64(h1)``; the
+    uniforms ``((h >> 40) + 1) 2^-24`` are exact in float64;
+    ``r = sqrt(-2 ln u1)`` and ``e = r cos(2 pi u2)``."""
+    if not torch.is_tensor(ctr):
+        ctr = torch.tensor(_i64(int(ctr)), dtype=torch.int64)
+    c = ctr.reshape(-1)[:1].to(device="cpu", dtype=torch.int64)
+    idx = torch.arange(B * A, dtype=torch.int64)
+    h1 = _sm64(c * 0x100000001 + idx * 2 + 1)
+    h2 = _sm64(h1)
+    u1 = (_lsr(h1, 40) + 1).double() * SQ_U
+    u2 = (_lsr(h2, 40) + 1).double() * SQ_U
+    r = torch.sqrt(-2.0 * torch.log(u1))
+    e = r * torch.cos(2.0 * math.pi * u2)
+    return e.reshape(B, A), r.reshape(B, A)
+
+
+@torch.no_grad()
+def squash_fwd_oracle(mu: torch.Tensor, lsr: torch.Tensor,
+                      eps: torch.Tensor, k: float,
+                      t: Optional[torch.Tensor] = None) -> dict:
+    """k_squash_fwd in float64 from its fp32 inputs ``mu, lsr, eps [B, A]``
+    (any strides).  Returns a dict:
+
+    - ``ls``: fp32, what ``ls_out`` must equal bit for bit —
+      ``clamp(lsr, -20, 2)``, a NaN staying a NaN;
+    - ``t, tol_t``: ``tanh(mu + exp(ls) eps)`` and
+      ``(1 - t^2) du + E_tanh u |t| + 2^-100`` with
+      ``du = (E_exp + 2) u |s e| + u |u64|`` (the error of s, the product
+      and the sum, carried through tanh's slope);
+    - ``logp, tol_logp [B, 1]``: the log-prob computed from the given
+      fp32 ``t`` (teacher forcing: the kernel's own saved tanh, so that the
+      ill-conditioned ``log(1 - t^2)`` is judged for its own arithmetic
+      only) or, without one, from ``t`` above.
+      ``tol = (3 A + E_log + 4) u mag + sum_a 2 u / w_a`` with
+      ``w = 1 - t^2 + 1e-6f`` and
+      ``mag = sum_a (e^2 / 2 + |ls| + C + |ln(k w)|)``; the second term
+      carries an absolute error u of ``1 - t t`` (fused or not) and of the
+      sum with 1e-6f through the logarithm, and is dropped where
+      ``t = +-1``: there ``1 - t t`` is exactly 0 in either order;
+    - ``act``: with a given ``t``, fp32 ``float32(k) t`` — one rounded
+      product, to be matched bit for bit."""
+    A = mu.shape[-1]
+    k32 = torch.tensor(float(k), dtype=torch.float32)
+    k64 = float(k32)
+    ls32 = torch.clamp(lsr.detach().float().cpu(), LOG_STD_MIN, LOG_STD_MAX)
+    ls = ls32.double()
+    e = eps.detach().cpu().double()
+    s = torch.exp(ls)
+    u64 = mu.detach().cpu().double() + s * e
+    t64 = torch.tanh(u64)
+    d_u = (SQ_E_EXP + 2) * SQ_U * (s * e).abs() + SQ_U * u64.abs()
+    tol_t = (1.0 - t64 * t64) * d_u + SQ_E_TANH * SQ_U * t64.abs() \
+        + GEMM_FLOOR
+    out = dict(ls=ls32, t=t64, tol_t=tol_t, act=None)
+    if t is not None:
+        t32 = t.detach().float().cpu()
+        out["act"] = k32 * t32
+        tt = t32.double()
+    else:
+        tt = t64
+    w = 1.0 - tt * tt + SQ_EPS6
+    lkw = torch.log(k64 * w)
+    out["logp"] = (-0.5 * e * e - ls - SQ_C - lkw).sum(-1, keepdim=True)
+    mag = (0.5 * e * e + ls.abs() + SQ_C + lkw.abs()).sum(-1, keepdim=True)
+    cond = torch.where(tt.abs() == 1.0, torch.zeros_like(w),
+                       2.0 * SQ_U / w).sum(-1, keepdim=True)
+    out["tol_logp"] = (3 * A + SQ_E_LOG + 4) * SQ_U * mag + cond
+    return out
+
+
+@torch.no_grad()
+def squash_bwd_oracle(ga: torch.Tensor, gl: torch.Tensor,
+                      lsr: torch.Tensor, ls: torch.Tensor,
+                      eps: torch.Tensor, t: torch.Tensor, k: float):
+    """``(du, dlsr, tol_du, tol_dlsr)`` float64 ``[B, A]`` of k_squash_bwd
+    and k_squash_bwd2 from their fp32 inputs: ``ga [B, A]`` or the twin
+    ``[2, B, A]`` (summed), ``gl [B]``, raw ``lsr``, and the forward's
+    saved ``ls, eps, t``.
+
+    ``du = T1 + T2``, ``T1 = ga k (1 - t^2)``,
+    ``T2 = g 2 t (1 - t^2) / w``, ``w = 1 - t^2 + 1e-6f``;
+    ``tol_du = 8 u (|T1| + |T2|) + u (|ga k| + |2 g t| 1e-6f / w^2)`` —
+    at most eight roundings on either term, and an absolute error u of
+    ``1 - t t`` through both terms' derivatives.
+    ``dlsr = m (du e s - g)`` with ``m = 1`` for raw ``lsr`` in [-20, 2],
+    0 outside (``tol = 0``: exactly 0) and NaN for a NaN;
+    ``tol_dlsr = tol_du |e s| + (E_exp + 4) u (|du e s| + |g|)``."""
+    k64 = float(torch.tensor(float(k), dtype=torch.float32))
+    ga64 = ga.detach().cpu().double()
+    if ga64.dim() == 3:
+        ga64 = ga64[0] + ga64[1]
+    g = gl.detach().cpu().double().reshape(-1, 1)
+    raw = lsr.detach().cpu().double()
+    e = eps.detach().cpu().double()
+    tt = t.detach().cpu().double()
+    s = torch.exp(ls.detach().cpu().double())
+    omt2 = 1.0 - tt * tt
+    w = omt2 + SQ_EPS6
+    T1 = ga64 * k64 * omt2
+    T2 = g * 2.0 * tt * omt2 / w
+    du = T1 + T2
+    tol_du = 8 * SQ_U * (T1.abs() + T2.abs()) + SQ_U * (
+        (ga64 * k64).abs() + (2.0 * g * tt).abs() * SQ_EPS6 / (w * w))
+    one, zero = torch.ones_like(raw), torch.zeros_like(raw)
+    inside = (raw >= LOG_STD_MIN) & (raw <= LOG_STD_MAX)
+    m = torch.where(inside, one, torch.where(torch.isnan(raw), raw, zero))
+    des = du * e * s
+    dlsr = m * (des - g)
+    tol_dlsr = torch.where(
+        inside,
+        tol_du * (e * s).abs() + (SQ_E_EXP + 4) * SQ_U * (des.abs() + g.abs()),
+        zero)
+    return du, dlsr, tol_du, tol_dlsr
+
+
+@torch.no_grad()
+def attn_pool_oracle(logits: torch.Tensor, z_encs: torch.Tensor,
+                     rep: int = 1):
+    """``(alpha, tol_alpha [Mz, E], pooled, tol_pooled [M, D])`` float64 of
+    k_attn_pool_fwd: ``alpha = softmax(logits [Mz, E])`` and
+    ``pooled[r] = sum_e alpha[r % Mz][e] z_encs[e][r]`` with
+    ``z_encs [E, M = Mz rep, D]``.  ``tol_alpha = (E + E_exp + 4) u alpha``
+    (the difference to the maximum, the exponential, E additions, the
+    reciprocal and the product); the pooled value is a GEMM of n = E terms
+    with ``mag = sum_e alpha_e |z_e|`` plus alpha's own error on ``mag``.
+    The output is bf16: use :func:`bound_ratio`."""
+    E = logits.shape[-1]
+    alpha = torch.softmax(logits.detach().cpu().double(), -1)
+    c_alpha = (E + SQ_E_EXP + 4) * SQ_U
+    tol_alpha = c_alpha * alpha + GEMM_FLOOR
+    z = z_encs.detach().cpu().double()
+    al = alpha.repeat(rep, 1)                     # row r -> alpha[r % Mz]
+    pooled = torch.einsum("me,emd->md", al, z)
+    mag = torch.einsum("me,emd->md", al, z.abs())
+    tol = (E + 2) * GEMM_ULP * mag + c_alpha * mag + GEMM_FLOOR
+    return alpha, tol_alpha, pooled, tol
+
+
+@torch.no_grad()
+def attn_pool_bwd_oracle(z_encs: torch.Tensor, alpha: torch.Tensor,
+                         dz: torch.Tensor):
+    """k_attn_pool_bwd from ``z_encs [E, M, D]`` fp32, ``alpha [M, E]`` fp32
+    and the bf16 ``dz [M, D]`` (the columns the kernel reads).  Returns
+    ``(dzencs_bits, dlogits, tol)``: the 16-bit words of
+    ``bf16_rne(float32(alpha_e dz))`` as int64 ``[E, M, D]`` — one rounded
+    product and one cast, to be matched bit for bit — and float64
+    ``dlogits = alpha_e (s_e - t)``, ``s_e = sum_d z_e dz``,
+    ``t = sum_e alpha_e s_e``, a GEMM of ``n = D + E + 4`` terms with
+    ``mag = alpha_e (sum_d |z_e dz| + sum_e' alpha_e' sum_d |z_e' dz|)``
+    (bf16 output)."""
+    E, M, D = z_encs.shape
+    a32 = alpha.detach().float().cpu()
+    dz32 = dz.detach().float().cpu()
+    prod = a32.t().unsqueeze(-1) * dz32.unsqueeze(0)          # fp32, RN
+    bits = f32_to_bf16_bits(prod.contiguous().view(torch.int32).long())
+    z, a, d = z_encs.detach().cpu().double(), a32.double(), dz32.double()
+    s = torch.einsum("emd,md->me", z, d)
+    sabs = torch.einsum("emd,md->me", z.abs(), d.abs())
+    t = (a * s).sum(-1, keepdim=True)
+    tabs = (a * sabs).sum(-1, keepdim=True)
+    dlogits = a * (s - t)
+    mag = a * (sabs + tabs)
+    tol = (D + E + 4 + 2) * GEMM_ULP * mag + GEMM_FLOOR
+    return bits, dlogits, tol

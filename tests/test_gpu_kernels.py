@@ -933,8 +933,12 @@ def test_chunked_capture_matches_sequential_replays():
 @pytest.mark.gpu
 def test_counter_rng_reproducible_and_distinct():
     """Counter RNG: same seed -> identical trajectories; consecutive
-    updates draw DIFFERENT noise (the counter advances in-graph); and
-    the squash eps written back is standard-normal-ish."""
+    updates draw DIFFERENT noise (the counter advances in-graph).  The
+    moment checks on the squash eps below are a coarse sanity check only:
+    that every element of the draw equals the hashed float64 Box-Muller
+    value is test_squash_reference.py::test_squash_counter_mode, and that
+    this value is standard normal and uncorrelated is
+    test_squash_oracle.py::test_eps_oracle_statistics."""
     from distributed_sac_amd import ops
     ext = ops.native()
     dev = "cuda:0"
