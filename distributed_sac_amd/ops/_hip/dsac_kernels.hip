@@ -658,6 +658,13 @@ __global__ __launch_bounds__(256) void k_squash_bwd(
 // alpha comes per-sample from log_alpha[t_i] (one_hots suffix of mtobs) —
 // no separate gather matmul (reference learner.get_log_alpha).
 // ---------------------------------------------------------------------------
+// twin minimum that keeps a NaN: fminf alone returns the other operand, so
+// a poisoned critic output would leave here as a valid number (torch.min
+// propagates it).  Every non-NaN pair gives fminf's bits.
+__device__ __forceinline__ float dsac_min_nan(float a, float b) {
+  return a != a ? a : (b != b ? b : fminf(a, b));
+}
+
 __global__ __launch_bounds__(256) void k_td_target(
     const float* __restrict__ r, const float* __restrict__ d,
     const float* __restrict__ q1, const float* __restrict__ q2,
@@ -665,7 +672,8 @@ __global__ __launch_bounds__(256) void k_td_target(
     float* __restrict__ y, int n, float gamma, float rs) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  y[i] = rs * r[i] + gamma * (1.f - d[i]) * (fminf(q1[i], q2[i]) - alpha[i] * lp[i]);
+  y[i] = rs * r[i] + gamma * (1.f - d[i])
+      * (dsac_min_nan(q1[i], q2[i]) - alpha[i] * lp[i]);
 }
 
 // y for one row, with the operation sequence spelled out (one fused
@@ -701,8 +709,8 @@ __global__ __launch_bounds__(256) void k_td_target_mt(
     }
   }
   const float alpha = __expf(log_alpha[t_i]);
-  y[i] = td_target_value(rs, r[i], gamma, d[i], fminf(q1[i], q2[i]), alpha,
-                         lp[i]);
+  y[i] = td_target_value(rs, r[i], gamma, d[i],
+                         dsac_min_nan(q1[i], q2[i]), alpha, lp[i]);
 }
 
 // ---------------------------------------------------------------------------
@@ -948,7 +956,7 @@ __global__ __launch_bounds__(256) void k_actor_alpha_loss_fwd_mb(
     const float alpha_i = __expf(la);
     const float w_raw = use_w ? smw[t_i] : 1.f;
     s_w += w_raw;
-    const float qmin = fminf(aq1[i], aq2[i]);
+    const float qmin = dsac_min_nan(aq1[i], aq2[i]);
     s_pl += w_raw * -(qmin - alpha_i * lp[i]);
     s_al += la * (lp[i] + H_bar);
     float ent = CE * A;
@@ -1009,7 +1017,7 @@ __global__ __launch_bounds__(256) void k_actor_alpha_loss_fwd_1wg(
     const float alpha_i = __expf(la);
     const float w_raw = use_w ? smw[t_i] : 1.f;
     s_w += w_raw;
-    const float qmin = fminf(aq1[i], aq2[i]);
+    const float qmin = dsac_min_nan(aq1[i], aq2[i]);
     s_pl += w_raw * -(qmin - alpha_i * lp[i]);
     s_al += la * (lp[i] + H_bar);
     float ent = CE * A;
@@ -1380,8 +1388,8 @@ __global__ __launch_bounds__(256) void k_critic_td_loss(
   float s_l1 = 0.f, s_l2 = 0.f, s_w = 0.f;
   if (i < B) {
     const float alpha = __expf(log_alpha[t_i]);
-    const float y = td_target_value(rs, rv, gamma, dv, fminf(q1tv, q2tv),
-                                    alpha, lpv);
+    const float y = td_target_value(rs, rv, gamma, dv,
+                                    dsac_min_nan(q1tv, q2tv), alpha, lpv);
     const float w_raw = use_w ? smw[t_i] : 1.f;
     s_w += w_raw;
     const float d1 = y - q1v, d2 = y - q2v;
@@ -1708,8 +1716,8 @@ __global__ __launch_bounds__(256) void k_critic_td_loss_per(
   float s_l1 = 0.f, s_l2 = 0.f, s_w = 0.f;
   if (i < B) {
     const float alpha = __expf(log_alpha[t_i]);
-    const float y = td_target_value(rs, rv, gamma, dv, fminf(q1tv, q2tv),
-                                    alpha, lpv);
+    const float y = td_target_value(rs, rv, gamma, dv,
+                                    dsac_min_nan(q1tv, q2tv), alpha, lpv);
     const float w_raw = use_w ? smw[t_i] : 1.f;
     s_w += w_raw;
     const float wi = w_raw * isn;
@@ -1960,7 +1968,7 @@ __global__ __launch_bounds__(256) void k_actor_alpha_loss_fwd_bwd(
     const float alpha_i = __expf(la);
     const float w_raw = use_w ? smw[t_i] : 1.f;
     s_w += w_raw;
-    const float qmin = fminf(aq1v, aq2v);
+    const float qmin = dsac_min_nan(aq1v, aq2v);
     s_pl += w_raw * -(qmin - alpha_i * lpv);
     s_al += la * (lpv + H_bar);
     s_en += ent;
@@ -2638,22 +2646,50 @@ static torch::Tensor td_target(torch::Tensor r, torch::Tensor d,
   return y;
 }
 
+// Argument checks shared by the K5-K7 bindings below (those of
+// critic_td_loss / actor_alpha_loss_fwd_bwd): the kernels take raw pointers
+// and read them with stride 1, so a view with other strides, a short
+// vector, T > 32 (smw[32]) or a dla longer than the 256 threads that zero
+// it must stop here, before any launch.
+static const float* loss_onehot_arg(const torch::Tensor& states,
+                                    const torch::Tensor& log_alpha, long B,
+                                    long T, const char* who) {
+  CHECK_IN(states); CHECK_IN(log_alpha);
+  TORCH_CHECK(B >= 1, who, ": B >= 1");
+  TORCH_CHECK(T >= 1 && T <= 32 && log_alpha.numel() >= T
+              && log_alpha.is_contiguous(), who,
+              ": 1 <= T <= 32 and T <= log_alpha.numel(), contiguous");
+  TORCH_CHECK(states.dim() == 2 && states.is_contiguous()
+              && states.size(0) == B && states.size(1) >= T, who,
+              ": states must be a contiguous [B, >= T] tensor");
+  return states.data_ptr<float>() + (states.size(1) - T);
+}
+
+static const float* loss_vec_arg(const torch::Tensor& t, long n,
+                                 const char* who, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32
+              && t.is_contiguous() && t.numel() == n, who, ": ", name,
+              " must be a contiguous fp32 HIP tensor of ", n, " elements");
+  return t.data_ptr<float>();
+}
+
 static torch::Tensor td_target_mt(torch::Tensor r, torch::Tensor d,
                                   torch::Tensor q1, torch::Tensor q2,
                                   torch::Tensor lp, torch::Tensor states,
                                   torch::Tensor log_alpha, long T,
                                   double gamma, double rs) {
-  CHECK_IN(r); CHECK_IN(states); CHECK_IN(log_alpha);
+  const char* who = "td_target_mt";
   const long n = r.numel();
+  const float* oh = loss_onehot_arg(states, log_alpha, n, T, who);
   const long oh_stride = states.size(1);
-  const float* oh = states.data_ptr<float>() + (oh_stride - T);
-  auto y = torch::empty_like(r.contiguous());
+  const float* r_p = loss_vec_arg(r, n, who, "r");
+  const float* d_p = loss_vec_arg(d, n, who, "d");
+  const float* q1_p = loss_vec_arg(q1, n, who, "q1");
+  const float* q2_p = loss_vec_arg(q2, n, who, "q2");
+  const float* lp_p = loss_vec_arg(lp, n, who, "lp");
+  auto y = torch::empty_like(r);
   hipLaunchKernelGGL(k_td_target_mt, dim3((n + 255) / 256), dim3(256), 0,
-                     cur_stream(), r.contiguous().data_ptr<float>(),
-                     d.contiguous().data_ptr<float>(),
-                     q1.contiguous().data_ptr<float>(),
-                     q2.contiguous().data_ptr<float>(),
-                     lp.contiguous().data_ptr<float>(), oh,
+                     cur_stream(), r_p, d_p, q1_p, q2_p, lp_p, oh,
                      log_alpha.data_ptr<float>(), y.data_ptr<float>(),
                      (int)n, (int)T, (int)oh_stride, (float)gamma,
                      (float)rs);
@@ -2664,25 +2700,28 @@ static std::vector<torch::Tensor> critic_loss_fwd(
     torch::Tensor q1, torch::Tensor q2, torch::Tensor y,
     torch::Tensor states, torch::Tensor log_alpha, long T, long use_w,
     c10::optional<torch::Tensor> ws = c10::nullopt) {
-  CHECK_IN(q1); CHECK_IN(states); CHECK_IN(log_alpha);
-  const long B = q1.size(0);
+  const char* who = "critic_loss_fwd";
+  const long B = q1.numel();
+  const float* oh = loss_onehot_arg(states, log_alpha, B, T, who);
   const long oh_stride = states.size(1);
-  const float* oh = states.data_ptr<float>() + (oh_stride - T);
+  const float* q1_p = loss_vec_arg(q1, B, who, "q1");
+  const float* q2_p = loss_vec_arg(q2, B, who, "q2");
+  const float* y_p = loss_vec_arg(y, B, who, "y");
   auto out = torch::empty({8}, q1.options());
   if (ws.has_value() && ws->numel() >= 1 + 32 * 3) {
+    CHECK_IN(*ws);
+    TORCH_CHECK(ws->is_contiguous(), who, ": ws must be contiguous");
     // persistent zero-initialized workspace -> multi-block one-launch
     // path with last-block finalize (ticket self-resets per launch)
     const int nblk = (int)std::min<long>((B + 255) / 256, 32);
     hipLaunchKernelGGL(k_critic_loss_fwd_mb, dim3(nblk), dim3(256), 0,
-                       cur_stream(), q1.data_ptr<float>(),
-                       q2.data_ptr<float>(), y.data_ptr<float>(), oh,
+                       cur_stream(), q1_p, q2_p, y_p, oh,
                        log_alpha.data_ptr<float>(), out.data_ptr<float>(),
                        ws->data_ptr<float>(), (int)B, (int)T,
                        (int)oh_stride, (int)use_w);
   } else {
     hipLaunchKernelGGL(k_critic_loss_fwd_1wg, dim3(1), dim3(256), 0,
-                       cur_stream(), q1.data_ptr<float>(),
-                       q2.data_ptr<float>(), y.data_ptr<float>(), oh,
+                       cur_stream(), q1_p, q2_p, y_p, oh,
                        log_alpha.data_ptr<float>(), out.data_ptr<float>(),
                        (int)B, (int)T, (int)oh_stride, (int)use_w);
   }
@@ -2693,16 +2732,20 @@ static std::vector<torch::Tensor> critic_loss_bwd(
     torch::Tensor q1, torch::Tensor q2, torch::Tensor y,
     torch::Tensor states, torch::Tensor log_alpha, torch::Tensor saved,
     torch::Tensor gscale, long T, long use_w) {
-  CHECK_IN(q1);
-  const long B = q1.size(0);
+  const char* who = "critic_loss_bwd";
+  const long B = q1.numel();
+  const float* oh = loss_onehot_arg(states, log_alpha, B, T, who);
   const long oh_stride = states.size(1);
-  const float* oh = states.data_ptr<float>() + (oh_stride - T);
+  const float* q1_p = loss_vec_arg(q1, B, who, "q1");
+  const float* q2_p = loss_vec_arg(q2, B, who, "q2");
+  const float* y_p = loss_vec_arg(y, B, who, "y");
+  const float* saved_p = loss_vec_arg(saved, 8, who, "saved");
+  const float* gscale_p = loss_vec_arg(gscale, 2, who, "gscale");
   auto dq1 = torch::empty_like(q1);
   auto dq2 = torch::empty_like(q2);
   hipLaunchKernelGGL(k_critic_loss_bwd, dim3((B + 255) / 256), dim3(256), 0,
-                     cur_stream(), q1.data_ptr<float>(), q2.data_ptr<float>(),
-                     y.data_ptr<float>(), oh, log_alpha.data_ptr<float>(),
-                     saved.data_ptr<float>(), gscale.data_ptr<float>(),
+                     cur_stream(), q1_p, q2_p, y_p, oh,
+                     log_alpha.data_ptr<float>(), saved_p, gscale_p,
                      dq1.data_ptr<float>(), dq2.data_ptr<float>(), (int)B,
                      (int)T, (int)oh_stride, (int)use_w);
   return {dq1, dq2};
@@ -2714,33 +2757,40 @@ static torch::Tensor actor_alpha_loss_fwd(
     double H_bar,
     c10::optional<torch::Tensor> dla = c10::nullopt,
     c10::optional<torch::Tensor> ws = c10::nullopt) {
-  CHECK_IN(aq1); CHECK_IN(states); CHECK_IN(log_alpha);
-  const long B = aq1.size(0);
-  const long A = ls.size(1);
+  const char* who = "actor_alpha_loss_fwd";
+  const long B = aq1.numel();
+  const float* oh = loss_onehot_arg(states, log_alpha, B, T, who);
   const long oh_stride = states.size(1);
-  const float* oh = states.data_ptr<float>() + (oh_stride - T);
+  const float* aq1_p = loss_vec_arg(aq1, B, who, "aq1");
+  const float* aq2_p = loss_vec_arg(aq2, B, who, "aq2");
+  const float* lp_p = loss_vec_arg(lp, B, who, "lp");
+  TORCH_CHECK(ls.dim() == 2 && ls.size(0) == B, who, ": ls must be [B, A]");
+  const long A = ls.size(1);
+  const float* ls_p = loss_vec_arg(ls, B * A, who, "ls");
   auto out = torch::empty({8}, aq1.options());
   float* dla_p = nullptr;
   int dla_n = 0;
   if (dla.has_value() && dla->numel() > 0) {
     CHECK_IN(*dla);
+    TORCH_CHECK(dla->numel() <= 256 && dla->is_contiguous(), who,
+                ": dla must be contiguous, at most 256 elements");
     dla_p = dla->data_ptr<float>();
     dla_n = (int)dla->numel();
   }
   if (ws.has_value() && ws->numel() >= 1 + 32 * 4) {
+    CHECK_IN(*ws);
+    TORCH_CHECK(ws->is_contiguous(), who, ": ws must be contiguous");
     const int nblk = (int)std::min<long>((B + 255) / 256, 32);
     hipLaunchKernelGGL(k_actor_alpha_loss_fwd_mb, dim3(nblk), dim3(256), 0,
-                       cur_stream(), aq1.data_ptr<float>(),
-                       aq2.data_ptr<float>(), lp.data_ptr<float>(),
-                       ls.data_ptr<float>(), oh, log_alpha.data_ptr<float>(),
+                       cur_stream(), aq1_p, aq2_p, lp_p, ls_p, oh,
+                       log_alpha.data_ptr<float>(),
                        out.data_ptr<float>(), ws->data_ptr<float>(), dla_p,
                        dla_n, (int)B, (int)T, (int)A, (int)oh_stride,
                        (int)use_w, (float)H_bar);
   } else {
     hipLaunchKernelGGL(k_actor_alpha_loss_fwd_1wg, dim3(1), dim3(256), 0,
-                       cur_stream(), aq1.data_ptr<float>(),
-                       aq2.data_ptr<float>(), lp.data_ptr<float>(),
-                       ls.data_ptr<float>(), oh, log_alpha.data_ptr<float>(),
+                       cur_stream(), aq1_p, aq2_p, lp_p, ls_p, oh,
+                       log_alpha.data_ptr<float>(),
                        out.data_ptr<float>(), dla_p, dla_n, (int)B, (int)T,
                        (int)A, (int)oh_stride, (int)use_w, (float)H_bar);
   }
@@ -2751,21 +2801,23 @@ static std::vector<torch::Tensor> actor_alpha_loss_bwd(
     torch::Tensor aq1, torch::Tensor aq2, torch::Tensor lp,
     torch::Tensor states, torch::Tensor log_alpha, torch::Tensor saved,
     torch::Tensor gscale, long T, long use_w, double H_bar) {
-  CHECK_IN(aq1);
-  const long B = aq1.size(0);
+  const char* who = "actor_alpha_loss_bwd";
+  const long B = aq1.numel();
+  const float* oh = loss_onehot_arg(states, log_alpha, B, T, who);
   const long oh_stride = states.size(1);
-  const float* oh = states.data_ptr<float>() + (oh_stride - T);
+  const float* aq1_p = loss_vec_arg(aq1, B, who, "aq1");
+  const float* aq2_p = loss_vec_arg(aq2, B, who, "aq2");
+  const float* lp_p = loss_vec_arg(lp, B, who, "lp");
+  const float* saved_p = loss_vec_arg(saved, 8, who, "saved");
+  const float* gscale_p = loss_vec_arg(gscale, 2, who, "gscale");
   auto daq1 = torch::empty_like(aq1);
   auto daq2 = torch::empty_like(aq2);
   auto dlp = torch::empty_like(lp);
   auto dla = torch::zeros_like(log_alpha);
-  TORCH_CHECK(T <= 32 && dla.numel() >= T, "alpha gradient: T <= 32");
   hipLaunchKernelGGL(k_actor_alpha_loss_bwd, dim3((B + 255) / 256 + 1), dim3(256),
                      (size_t)T * 256 * sizeof(float), cur_stream(),
-                     aq1.data_ptr<float>(),
-                     aq2.data_ptr<float>(), lp.data_ptr<float>(), oh,
-                     log_alpha.data_ptr<float>(), saved.data_ptr<float>(),
-                     gscale.data_ptr<float>(), daq1.data_ptr<float>(),
+                     aq1_p, aq2_p, lp_p, oh, log_alpha.data_ptr<float>(),
+                     saved_p, gscale_p, daq1.data_ptr<float>(),
                      daq2.data_ptr<float>(), dlp.data_ptr<float>(),
                      dla.data_ptr<float>(), (int)B, (int)T, (int)oh_stride,
                      (int)use_w, (float)H_bar);
@@ -2776,15 +2828,18 @@ static torch::Tensor critic_loss_bwd2(
     torch::Tensor q1, torch::Tensor q2, torch::Tensor y,
     torch::Tensor states, torch::Tensor log_alpha, torch::Tensor saved,
     long T, long use_w) {
-  CHECK_IN(q1);
-  const long B = q1.size(0);
+  const char* who = "critic_loss_bwd2";
+  const long B = q1.numel();
+  const float* oh = loss_onehot_arg(states, log_alpha, B, T, who);
   const long oh_stride = states.size(1);
-  const float* oh = states.data_ptr<float>() + (oh_stride - T);
+  const float* q1_p = loss_vec_arg(q1, B, who, "q1");
+  const float* q2_p = loss_vec_arg(q2, B, who, "q2");
+  const float* y_p = loss_vec_arg(y, B, who, "y");
+  const float* saved_p = loss_vec_arg(saved, 8, who, "saved");
   auto dq = torch::empty({2, B, 1}, q1.options().dtype(torch::kBFloat16));
   hipLaunchKernelGGL(k_critic_loss_bwd2, dim3((B + 255) / 256), dim3(256), 0,
-                     cur_stream(), q1.data_ptr<float>(), q2.data_ptr<float>(),
-                     y.data_ptr<float>(), oh, log_alpha.data_ptr<float>(),
-                     saved.data_ptr<float>(),
+                     cur_stream(), q1_p, q2_p, y_p, oh,
+                     log_alpha.data_ptr<float>(), saved_p,
                      (unsigned short*)dq.data_ptr(), (int)B, (int)T,
                      (int)oh_stride, (int)use_w);
   return dq;
@@ -2795,26 +2850,32 @@ static std::vector<torch::Tensor> actor_alpha_loss_bwd2(
     torch::Tensor states, torch::Tensor log_alpha, torch::Tensor saved,
     torch::Tensor dla_out, long T, long use_w, double H_bar,
     c10::optional<torch::Tensor> ws = c10::nullopt) {
-  CHECK_IN(aq1); CHECK_IN(dla_out);
-  const long B = aq1.size(0);
+  const char* who = "actor_alpha_loss_bwd2";
+  CHECK_IN(dla_out);
+  const long B = aq1.numel();
+  const float* oh = loss_onehot_arg(states, log_alpha, B, T, who);
   const long oh_stride = states.size(1);
-  const float* oh = states.data_ptr<float>() + (oh_stride - T);
+  const float* aq1_p = loss_vec_arg(aq1, B, who, "aq1");
+  const float* aq2_p = loss_vec_arg(aq2, B, who, "aq2");
+  const float* lp_p = loss_vec_arg(lp, B, who, "lp");
+  const float* saved_p = loss_vec_arg(saved, 8, who, "saved");
+  TORCH_CHECK(dla_out.numel() >= T && dla_out.is_contiguous(), who,
+              ": dla_out must be contiguous with at least T elements");
   auto daq = torch::empty({2, B, 1}, aq1.options().dtype(torch::kBFloat16));
   auto dlp = torch::empty_like(lp);
-  TORCH_CHECK(T <= 32 && dla_out.numel() >= T, "alpha gradient: T <= 32");
   const long nblk = (B + 255) / 256;
   float* ws_p = nullptr;   // ticket path only if the workspace is big enough
   if (ws.has_value() && ws->numel() >= 1 + nblk * T) {
     CHECK_IN(*ws);
+    TORCH_CHECK(ws->is_contiguous(), who, ": ws must be contiguous");
     ws_p = ws->data_ptr<float>();
   }
   hipLaunchKernelGGL(k_actor_alpha_loss_bwd2,
                      dim3(ws_p ? nblk : nblk + 1),
                      dim3(256),
                      ws_p ? 0 : (size_t)T * 256 * sizeof(float),
-                     cur_stream(), aq1.data_ptr<float>(),
-                     aq2.data_ptr<float>(), lp.data_ptr<float>(), oh,
-                     log_alpha.data_ptr<float>(), saved.data_ptr<float>(),
+                     cur_stream(), aq1_p, aq2_p, lp_p, oh,
+                     log_alpha.data_ptr<float>(), saved_p,
                      (unsigned short*)daq.data_ptr(), dlp.data_ptr<float>(),
                      dla_out.data_ptr<float>(), ws_p, (int)B, (int)T,
                      (int)oh_stride, (int)use_w, (float)H_bar);

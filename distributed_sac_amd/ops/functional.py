@@ -215,8 +215,9 @@ class _CriticLoss(torch.autograd.Function):
                 use_weighted: bool):
         ext = native()
         out = ext.critic_loss_fwd(q1.contiguous(), q2.contiguous(),
-                                  y.contiguous(), states, log_alpha_det,
-                                  num_tasks, int(use_weighted))[0]
+                                  y.contiguous(), states.contiguous(),
+                                  log_alpha_det, num_tasks,
+                                  int(use_weighted))[0]
         ctx.save_for_backward(q1, q2, y, states, log_alpha_det, out)
         ctx.meta = (num_tasks, use_weighted)
         return out[0], out[1]
@@ -227,8 +228,8 @@ class _CriticLoss(torch.autograd.Function):
         T, use_w = ctx.meta
         gscale = torch.stack([g1.reshape(()), g2.reshape(())]).contiguous()
         dq1, dq2 = native().critic_loss_bwd(
-            q1.contiguous(), q2.contiguous(), y.contiguous(), states, la,
-            saved, gscale, T, int(use_w))
+            q1.contiguous(), q2.contiguous(), y.contiguous(),
+            states.contiguous(), la, saved, gscale, T, int(use_w))
         return dq1, dq2, None, None, None, None, None
 
 
@@ -263,8 +264,8 @@ class _ActorAlphaLoss(torch.autograd.Function):
         ext = native()
         out = ext.actor_alpha_loss_fwd(
             q1.contiguous(), q2.contiguous(), logp.contiguous(),
-            log_stds.contiguous(), states, log_alpha.detach(), num_tasks,
-            int(use_weighted), H_bar)
+            log_stds.contiguous(), states.contiguous(), log_alpha.detach(),
+            num_tasks, int(use_weighted), H_bar)
         ctx.save_for_backward(q1, q2, logp, states, log_alpha.detach(), out)
         ctx.meta = (num_tasks, use_weighted, H_bar)
         actor_l, alpha_l, entropy = out[0], out[2], out[3]
@@ -277,8 +278,8 @@ class _ActorAlphaLoss(torch.autograd.Function):
         T, use_w, H_bar = ctx.meta
         gscale = torch.stack([gp.reshape(()), gal.reshape(())]).contiguous()
         daq1, daq2, dlp, dla = native().actor_alpha_loss_bwd(
-            q1.contiguous(), q2.contiguous(), logp.contiguous(), states, la,
-            saved, gscale, T, int(use_w), H_bar)
+            q1.contiguous(), q2.contiguous(), logp.contiguous(),
+            states.contiguous(), la, saved, gscale, T, int(use_w), H_bar)
         return daq1, daq2, dlp, None, None, dla, None, None, None
 
 

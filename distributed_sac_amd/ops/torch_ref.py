@@ -878,3 +878,287 @@ def attn_pool_bwd_oracle(z_encs: torch.Tensor, alpha: torch.Tensor,
     mag = a * (sabs + tabs)
     tol = (D + E + 4 + 2) * GEMM_ULP * mag + GEMM_FLOOR
     return bits, dlogits, tol
+
+
+# ---------------------------------------------------------------------------
+# TD-target and loss oracles (K5-K7; docs/KERNELS.md "Numerics").  Float64
+# references of k_td_target(_mt), k_critic_loss_*, k_actor_alpha_loss_* and
+# the two fused-tail kernels, each next to a bound in units of u = 2^-24
+# derived from the kernels' operation sequence.  Elementwise outputs get one
+# rounding per operation on its own magnitude plus the propagated input
+# error; a sum S of fp32 terms gets
+#     |S - S64| <= sum |dterm_i| + (L + 2) u sum |term_i|,
+# L the longest chain of dependent additions (:func:`loss_chain`).  The one
+# allowance that is no plain rounding is __expf, v_exp_f32(x log2e) on
+# gfx950: relative E_fexp(x) u = (LOSS_E_FEXP + 2 |x|) u, the product's
+# rounding scaled by |x| plus the instruction's error.  The constant part
+# started at 4 (a 1-ulp instruction, 2 u, doubled); measured on the device
+# over the tests' log_alpha the worst error is 3.945 u, more than a quarter
+# of that allowance, so it is four times the worst observed, rounded up:
+# 16 (profiles/loss_reference.md).  Constants are the
+# kernels' fp32 constants widened.  Backward coefficients are judged from
+# the wsum the kernel was handed, sums from the y they were given.
+# ---------------------------------------------------------------------------
+
+LOSS_CE = float(torch.tensor(1.4189385332046727, dtype=torch.float32))
+LOSS_E_FEXP = 16.0
+
+
+def _f32(v) -> float:
+    return float(torch.tensor(float(v), dtype=torch.float32))
+
+
+def _vec64(x: torch.Tensor) -> torch.Tensor:
+    return x.detach().cpu().double().reshape(-1)
+
+
+def loss_e_fexp(x: torch.Tensor) -> torch.Tensor:
+    """Relative error bound of the kernels' ``__expf(x)``."""
+    return (LOSS_E_FEXP + 2.0 * x.abs()) * SQ_U
+
+
+def loss_task_index(states: torch.Tensor, T: int) -> torch.Tensor:
+    """Task of every row, int64 ``[B]``: the position of the FIRST maximum
+    of the last ``T`` columns (an all-zero row is task 0); 0 for T == 1."""
+    st = states.detach().cpu()
+    B = st.shape[0]
+    if T <= 1:
+        return torch.zeros(B, dtype=torch.int64)
+    suf = st[:, st.shape[1] - T:]
+    mx = suf.max(-1, keepdim=True).values
+    pos = torch.arange(T).expand(B, T)
+    return torch.where(suf == mx, pos, torch.full_like(pos, T)).min(-1).values
+
+
+def loss_chain(B: int, kind: str, nblk: int = 1) -> int:
+    """Longest chain of dependent fp32 additions of a reduction over B
+    rows.  ``mb`` (k_*_loss_fwd_mb and the fused kernels, nblk blocks):
+    per-thread strided adds, 6 butterfly steps, 3 adds of the four wave
+    partials, nblk slots.  ``1wg``: the same in one block, no slots.
+    ``agb`` (alpha_grad_block): per-thread adds, 2 for the four LDS
+    columns, 6 butterfly steps.  ``ws`` (per-block task sums of
+    k_actor_alpha_loss_bwd2 / the fused kernel): 2 + 6 + nblk slots."""
+    if kind == "mb":
+        return -(-B // (256 * nblk)) + 6 + 3 + nblk
+    if kind == "1wg":
+        return -(-B // 256) + 6 + 3
+    if kind == "agb":
+        return -(-B // 256) + 2 + 6
+    if kind == "ws":
+        return 2 + 6 + nblk
+    raise ValueError(kind)
+
+
+def loss_alpha(log_alpha: torch.Tensor, T: int):
+    """``(alpha, e_alpha) [T]``: float64 ``exp(log_alpha)`` and the relative
+    error bound of the kernels' ``__expf``."""
+    la = _vec64(log_alpha)[:T]
+    return torch.exp(la), loss_e_fexp(la)
+
+
+def loss_task_weights(log_alpha: torch.Tensor, T: int):
+    """``(w, e_w) [T]``: float64 ``softmax(-exp(log_alpha))`` and the
+    relative error bound of fill_task_weights.  With ``a = exp(la)`` (error
+    ``a e_a``) and ``m = min a`` the exponent ``z = m - a`` carries
+    ``dz = u |z| + a e_a + m e_m``, so a numerator is off by
+    ``rho = E_fexp(z) u + dz``; the denominator by ``max rho`` plus T - 1
+    additions; one more rounding for the division."""
+    a, e_a = loss_alpha(log_alpha, T)
+    k = int(torch.argmin(a))
+    z = a[k] - a
+    dz = SQ_U * z.abs() + a * e_a + a[k] * e_a[k]
+    rho = loss_e_fexp(z) + dz
+    ex = torch.exp(z)
+    return ex / ex.sum(), rho + rho.max() + (T + 1) * SQ_U
+
+
+def loss_sum(term: torch.Tensor, dterm: torch.Tensor, L: int):
+    """``(S, tol)`` of an fp32 sum whose longest addition chain is L."""
+    return term.sum(), dterm.sum() + (L + 2) * SQ_U * term.abs().sum() \
+        + GEMM_FLOOR
+
+
+@torch.no_grad()
+def td_target_oracle(r, d, q1, q2, lp, gamma: float, rs: float,
+                     alpha: Optional[torch.Tensor] = None,
+                     states: Optional[torch.Tensor] = None,
+                     log_alpha: Optional[torch.Tensor] = None, T: int = 1):
+    """``(y, tol)`` float64 ``[B]``:
+    ``y = rs r + gamma (1 - d) (min(q1, q2) - alpha lp)``, a NaN in either
+    Q staying one.  With ``states, log_alpha, T`` it is k_td_target_mt /
+    td_target_value: ``alpha = exp(log_alpha[task])`` carries
+    ``dalpha = alpha E_fexp u`` and ``x = fma(-alpha, lp, qmin)`` one
+    rounding, ``dx = u |x| + dalpha |lp|``.  With a per-sample ``alpha`` it
+    is k_td_target, whose contraction is the compiler's: the product
+    ``alpha lp`` may round on its own (``+ u |alpha lp|``), and every other
+    fusion only removes a rounding.  Then ``g = gamma (1 - d)`` (``1 - d``
+    exact for d in {0, 1}), ``p = g x``, ``q = rs r``, ``y = q + p``:
+    ``tol = u (|q| + 2 |p| + |y|) + |g| dx (+ u gamma |1 - d| |x|)``."""
+    r, d, q1, q2, lp = (_vec64(v) for v in (r, d, q1, q2, lp))
+    if alpha is not None:
+        a = _vec64(alpha)
+        da = torch.zeros_like(a)
+    else:
+        t = loss_task_index(states, T)
+        a_t, e_t = loss_alpha(log_alpha, T)
+        a, da = a_t[t], (a_t * e_t)[t]
+    g32, s32 = _f32(gamma), _f32(rs)
+    x = torch.minimum(q1, q2) - a * lp
+    dx = SQ_U * x.abs() + da * lp.abs()
+    if alpha is not None:
+        dx = dx + SQ_U * (a * lp).abs()
+    omd = 1.0 - d
+    d_omd = torch.where((d == 0) | (d == 1), torch.zeros_like(d),
+                        SQ_U * omd.abs())
+    g = g32 * omd
+    p, q = g * x, s32 * r
+    y = q + p
+    tol = SQ_U * (q.abs() + 2.0 * p.abs() + y.abs()) + g.abs() * dx \
+        + g32 * d_omd * x.abs() + GEMM_FLOOR
+    return y, tol
+
+
+def _loss_rows(states, log_alpha, T: int, use_w: int, B: int):
+    """Per-row task, weight and the weight's relative error."""
+    t = loss_task_index(states, T)
+    if use_w:
+        w_t, e_t = loss_task_weights(log_alpha, T)
+        return t, w_t[t], e_t[t]
+    return t, torch.ones(B, dtype=torch.float64), \
+        torch.zeros(B, dtype=torch.float64)
+
+
+@torch.no_grad()
+def critic_loss_oracle(q1, q2, y, states, log_alpha, T: int, use_w: int,
+                       L: int, wsum: Optional[float] = None,
+                       gscale=None) -> dict:
+    """The critic loss kernels in float64 from the fp32 ``q1, q2, y [B]``
+    they are given.  ``out, tol_out [7]``: ``r0 = sum w (y - q1)^2``,
+    ``r1`` likewise, ``r2 = sum w`` at 3, 4, 5 (a term is off by
+    ``(4 u + e_w) |term|``: the difference twice, two products, the
+    weight); ``out[2] = r2`` or exactly 1 without weights;
+    ``out[0, 1] = r / (out[2] B)`` and ``out[6] = (r0 + r1) / (out[2] B)``
+    add r2's relative error and the roundings of the product, the division
+    (and the sum).  With ``wsum`` — the fp32 value the backward was
+    handed — also ``dq, tol_dq [2, B]``:
+    ``dq = g (w / wsum / B) (-2) (y - q)``, relative
+    ``e_w + 4 u`` (``+ u`` with a ``gscale``, ``- u`` without weights)."""
+    q1, q2, y = (_vec64(v) for v in (q1, q2, y))
+    B = q1.numel()
+    _, w, ew = _loss_rows(states, log_alpha, T, use_w, B)
+    d1, d2 = y - q1, y - q2
+    t1, t2 = w * d1 * d1, w * d2 * d2
+    rel = 4 * SQ_U + ew
+    S0, tol0 = loss_sum(t1, rel * t1.abs(), L)
+    S1, tol1 = loss_sum(t2, rel * t2.abs(), L)
+    Sw, tolw = loss_sum(w, ew * w, L)
+    one, zero = torch.tensor(1.0, dtype=torch.float64), \
+        torch.tensor(0.0, dtype=torch.float64)
+    ws, tws = (Sw, tolw) if use_w else (one, zero)
+    rel_w = tws / ws
+    den = ws * B
+    o0, o1, o6 = S0 / den, S1 / den, (S0 + S1) / den
+    res = dict(
+        out=torch.stack([o0, o1, ws, S0, S1, Sw, o6]),
+        tol_out=torch.stack([
+            tol0 / den + o0.abs() * (rel_w + 2 * SQ_U),
+            tol1 / den + o1.abs() * (rel_w + 2 * SQ_U),
+            tws, tol0, tol1, tolw,
+            (tol0 + tol1) / den + o6.abs() * (rel_w + 3 * SQ_U)]))
+    if wsum is not None:
+        c = (w / float(wsum) if use_w else w) / B
+        relc = ew + (4 if use_w else 3) * SQ_U
+        g = [1.0, 1.0]
+        if gscale is not None:
+            g = [_f32(v) for v in torch.as_tensor(gscale).reshape(-1).tolist()]
+            relc = relc + SQ_U
+        dq = torch.stack([g[0] * c * -2.0 * d1, g[1] * c * -2.0 * d2])
+        res.update(dq=dq, tol_dq=dq.abs() * relc + GEMM_FLOOR)
+    return res
+
+
+@torch.no_grad()
+def actor_alpha_loss_oracle(aq1, aq2, lp, ls, states, log_alpha, T: int,
+                            use_w: int, H_bar: float, L: int,
+                            wsum: Optional[float] = None, gscale=None,
+                            L_dla: Optional[int] = None,
+                            dla_n: Optional[int] = None) -> dict:
+    """The actor / alpha loss kernels in float64 from their fp32 inputs.
+
+    ``out, tol_out [8]``: the raw sums at 4..7 —
+    ``s_pl = sum -w (min(aq1, aq2) - alpha lp)`` (a NaN Q staying one; a
+    term is off by ``w (u |alpha lp| + dalpha |lp| + u |x|) + (u + e_w)
+    |term|``), ``s_w = sum w``, ``s_al = sum la (lp + H)`` (``2 u |term|``),
+    ``s_en = sum (CE A + sum_a ls)`` (one rounding per partial sum) — and
+    ``out[0] = s_pl / (out[1] B)``, ``out[1] = s_w`` or exactly 1,
+    ``out[2] = -s_al / B``, ``out[3] = s_en / B``.  The bounds of the
+    signed sums are on ``sum |term|``.
+
+    With ``wsum`` (the fp32 value the backward used) the backward:
+    ``c = w / wsum / B``; ``daq [2, B]`` holds ``-g c`` in the twin with the
+    smaller Q (the first on a tie, the second beside a NaN) and an exact 0
+    in the other; ``dlp = g c alpha``.  Without weights and ``gscale``,
+    ``daq_bits`` is the 16-bit word of ``bf16_rne(float32(-1 / B))``, to be
+    matched bit for bit.  With ``L_dla`` the alpha gradient ``dla [dla_n]``:
+    ``sum_{i in t} gal (-(lp + H)) / B`` per task (two roundings a term,
+    three with a ``gscale``), exactly 0 for a task without rows and past
+    T."""
+    aq1, aq2, lp = (_vec64(v) for v in (aq1, aq2, lp))
+    ls = ls.detach().cpu().double()
+    B, A = aq1.numel(), ls.shape[1]
+    t, w, ew = _loss_rows(states, log_alpha, T, use_w, B)
+    a_t, e_t = loss_alpha(log_alpha, T)
+    la = _vec64(log_alpha)[:T][t]
+    al, e_al = a_t[t], e_t[t]
+    H = _f32(H_bar)
+    x = torch.minimum(aq1, aq2) - al * lp
+    dx = SQ_U * (al * lp).abs() + al * e_al * lp.abs() + SQ_U * x.abs()
+    t_pl = -w * x
+    S0, tol0 = loss_sum(t_pl, w * dx + t_pl.abs() * (SQ_U + ew), L)
+    Sw, tolw = loss_sum(w, ew * w, L)
+    t_al = la * (lp + H)
+    S2, tol2 = loss_sum(t_al, 2 * SQ_U * t_al.abs(), L)
+    part = torch.cumsum(
+        torch.cat([torch.full((B, 1), LOSS_CE * A, dtype=torch.float64),
+                   ls.reshape(B, A)], 1), 1)
+    S3, tol3 = loss_sum(part[:, -1], SQ_U * part.abs().sum(1), L)
+    one, zero = torch.tensor(1.0, dtype=torch.float64), \
+        torch.tensor(0.0, dtype=torch.float64)
+    ws, tws = (Sw, tolw) if use_w else (one, zero)
+    den = ws * B
+    o0, o2, o3 = S0 / den, -S2 / B, S3 / B
+    res = dict(
+        out=torch.stack([o0, ws, o2, o3, S0, Sw, S2, S3]),
+        tol_out=torch.stack([
+            tol0 / den + o0.abs() * (tws / ws + 2 * SQ_U), tws,
+            tol2 / B + SQ_U * o2.abs(), tol3 / B + SQ_U * o3.abs(),
+            tol0, tolw, tol2, tol3]))
+    g = [1.0, 1.0]
+    rg = 0.0
+    if gscale is not None:
+        g = [_f32(v) for v in torch.as_tensor(gscale).reshape(-1).tolist()]
+        rg = SQ_U
+    if wsum is not None:
+        c = (w / float(wsum) if use_w else w) / B
+        relc = (ew + 2 * SQ_U if use_w else SQ_U) + rg
+        first = aq1 <= aq2
+        v = -g[0] * c
+        z = torch.zeros_like(v)
+        daq = torch.stack([torch.where(first, v, z), torch.where(first, z, v)])
+        dlp = g[0] * c * al
+        res.update(daq=daq, tol_daq=daq.abs() * relc, dlp=dlp,
+                   tol_dlp=dlp.abs() * (relc + SQ_U + e_al) + GEMM_FLOOR)
+        if not use_w and gscale is None:
+            c32 = -(torch.tensor(1.0) / torch.tensor(float(B)))
+            bits = f32_to_bf16_bits(c32.view(torch.int32).long())
+            zb = torch.zeros(B, dtype=torch.int64)
+            res["daq_bits"] = torch.stack([torch.where(first, bits, zb),
+                                           torch.where(first, zb, bits)])
+    if L_dla is not None:
+        n = T if dla_n is None else dla_n
+        term = g[1] * -(lp + H) / B
+        nr = 3 if gscale is not None else 2
+        dla = torch.zeros(n, dtype=torch.float64).index_add_(0, t, term)
+        mag = torch.zeros(n, dtype=torch.float64).index_add_(0, t, term.abs())
+        res.update(dla=dla, tol_dla=(nr + L_dla + 2) * SQ_U * mag)
+    return res
