@@ -259,8 +259,7 @@ class CAREEngine(SACEngine):
 
     # -- bf16 fast state-encoder machinery ------------------------------
     def _init_care_bf16(self) -> None:
-        if not getattr(self, "_bf16", False):
-            self._se_fast = False
+        if not self._bf16:
             return
         self._se_fast = True
         dev = self.device
@@ -312,7 +311,6 @@ class CAREEngine(SACEngine):
         # so the manual path can run the context chain on the fused chain
         # kernels (fwd + dx + grouped dwdb, third arena) — in both
         # DSAC_CHAIN modes
-        self._ctx_chain = None
         if self.context_group is not None:
             lins = mlp_linears(self.context_encoder.modules())
             grp = self.context_group
@@ -328,7 +326,7 @@ class CAREEngine(SACEngine):
 
     @torch.no_grad()
     def _refresh_mixT(self, which: str = "all") -> None:
-        if not getattr(self, "_se_fast", False):
+        if not self._se_fast:
             return
         if which in ("all", "critic"):
             for m, W in zip(self._se_local["mixT"], self._se_local["mixW"]):
@@ -341,7 +339,7 @@ class CAREEngine(SACEngine):
     def refresh_bf16(self, which: str = "all") -> None:
         super().refresh_bf16(which)
         self._refresh_mixT(which)
-        if which == "all" and getattr(self, "_ctx_chain", None) is not None:
+        if which == "all" and self._ctx_chain is not None:
             self._ctx_bf16.copy_(self.context_group.flat_data)
 
     def _se_fwd_fast(self, info, mtobss_2d, z_context):
@@ -366,7 +364,7 @@ class CAREEngine(SACEngine):
         return torch.cat([zc, z_enc], dim=1)
 
     def _twin_fwd(self, x, which: str):
-        if getattr(self, "_bf16", False):
+        if self._bf16:
             if which == "target":
                 return Fops.twin_mlp_forward_bf16(x, *self._twin_target,
                                                   self._target_chain.ws16)
@@ -388,9 +386,9 @@ class CAREEngine(SACEngine):
         under no_grad (see module doc); the actor head runs ONE batched
         pass over cat(next, states) like the SAC engine (the actor-side
         state encoder is no-grad in both halves)."""
-        manual_ok = getattr(self, "_se_fast", False) and (
+        manual_ok = self._se_fast and (
             self.use_modified_care
-            or getattr(self, "_ctx_chain", None) is not None)
+            or self._ctx_chain is not None)
         if manual_ok and os.environ.get("DSAC_NO_MANUAL", "0") != "1":
             return self._update_tensors_manual(batch)
         from ..ops import native
@@ -412,7 +410,7 @@ class CAREEngine(SACEngine):
         # states half doubles as the critic-loss encoding (with grad), and
         # a detached copy feeds the actor head.
         x_cat = torch.cat([next_states, states], dim=0)
-        if getattr(self, "_se_fast", False):
+        if self._se_fast:
             z2 = torch.cat([z_context, z_context], dim=0)
             enc_cat = self._se_fwd_fast(self._se_local, x_cat, z2)
         else:
@@ -421,9 +419,9 @@ class CAREEngine(SACEngine):
                 enc_cat = self.actor.state_encoder(z2, x_cat,
                                                    detach_z_encs=True)
         ws, bs = self._actor_weights()
-        enc_actor_in = (enc_cat.detach() if getattr(self, "_se_fast", False)
+        enc_actor_in = (enc_cat.detach() if self._se_fast
                         else enc_cat)
-        if getattr(self, "_bf16", False):
+        if self._bf16:
             mu_lsr = Fops.mlp_forward_bf16(enc_actor_in, ws, bs,
                                            self._actor_ws_bf16,
                                            grad_row_start=B)
@@ -431,17 +429,13 @@ class CAREEngine(SACEngine):
             mu_lsr = Fops.mlp_forward(enc_actor_in, ws, bs, grad_row_start=B)
         mu = mu_lsr[:, :A]
         lsr = mu_lsr[:, A:]
-        if self._eps_queue:
-            eps = torch.cat([self._next_eps(mu[:B]), self._next_eps(mu[:B])])
-        else:
-            eps = torch.randn_like(mu)
-        a_cat, lp_cat, ls_cat = Fops.squashed_gaussian(mu, lsr, eps,
-                                                       self.actor.k)
+        a_cat, lp_cat, ls_cat = Fops.squashed_gaussian(
+            mu, lsr, self._eps_cat(mu, B), self.actor.k)
         na, nlp = a_cat[:B].detach(), lp_cat[:B].detach()
         sa, lp, ls = a_cat[B:], lp_cat[B:], ls_cat[B:]
 
         with torch.no_grad():
-            if getattr(self, "_se_fast", False):
+            if self._se_fast:
                 enc_t = self._se_fwd_fast(self._se_target, next_states,
                                           z_context)
             else:
@@ -452,7 +446,7 @@ class CAREEngine(SACEngine):
                                       states, self.log_alpha.detach(), T,
                                       self.gamma, self.reward_scale)
 
-        if getattr(self, "_se_fast", False):
+        if self._se_fast:
             enc = enc_cat[B:]
         else:
             enc = self.local_critic.encode(states, z_context)
@@ -462,15 +456,12 @@ class CAREEngine(SACEngine):
                                   T, use_w)
         q_loss = l1 + l2
         q_loss.backward()
-        if self.ddp is not None:
-            self.ddp.allreduce_grad_(self.critic_group.flat_grad)
-            if self.context_group is not None:
-                self.ddp.allreduce_grad_(self.context_group.flat_grad)
+        self._allreduce_critic_grads()
         self.critic_optimizer.step()
         self.refresh_bf16("critic")
 
         with torch.no_grad():
-            if getattr(self, "_se_fast", False):
+            if self._se_fast:
                 enc_c = self._se_fwd_fast(self._se_local, states, zc_d)
             else:
                 enc_c = self.local_critic.encode(states, zc_d,
@@ -618,60 +609,41 @@ class CAREEngine(SACEngine):
                              alpha=alpha, acts_c=acts_c, rep=rep)
         return enc, None
 
-    @torch.no_grad()
-    def _update_tensors_manual(self, batch):
-        """CARE bf16 update with a HAND-ROLLED backward (both variants:
-        CARE(M) frozen context, original CARE trainable context encoder),
-        structured as three SEGMENTS split at the DP all-reduce
-        boundaries so capture_dp (inherited from SACEngine) can hipGraph
-        each segment with eager RCCL between replays:
-          seg1: z_context + SE/actor forwards + TD + critic(+context)
-                backward -> critic (+ context) grads
-          seg2: critic Adam + actor-side forward/backward -> aa grads
-          seg3: actor/alpha Adam + Polyak + context Adam + SE tie
-        (reference gradient-flow rules: MT10_Distributed_CARE/src/
-        learner.py:281-404 — trunk input detached, actor optimizes only
-        its head, context grads from the critic loss only)."""
-        self._manual_seg1(batch)
-        if self.ddp is not None:
-            self.ddp.allreduce_grad_(self.critic_group.flat_grad)
-            if self._dp_st.get("orig") and self.context_group is not None:
-                self.ddp.allreduce_grad_(self.context_group.flat_grad)
-        self._manual_seg2()
-        if self.ddp is not None:
-            self.ddp.allreduce_grad_(self._aa_arena)
-        return self._manual_seg3()
+    # The three-segment manual update itself is SACEngine's
+    # (_update_tensors_manual, capture_dp, dp_graphed_update); CARE
+    # brings its own seg1 and seg2 head and the hooks below.
+    @property
+    def _fuse_tail(self) -> bool:
+        # CARE keeps the separate tail launches it has always had: nobody
+        # has measured it on the fused tail
+        return False
 
-    def dp_graphed_update(self):
-        """Segmented DP replay with CARE's extra context all-reduce."""
-        g1, g2, g3 = self._dp_graphs
-        g1.replay()
-        if self.ddp is not None:
-            self.ddp.allreduce_grad_(self.critic_group.flat_grad)
-            if (not self.use_modified_care
-                    and self.context_group is not None):
-                self.ddp.allreduce_grad_(self.context_group.flat_grad)
-        g2.replay()
-        if self.ddp is not None:
-            self.ddp.allreduce_grad_(self._aa_arena)
-        g3.replay()
-        self.update_iteration += 1
-        return self._dp_graph_metrics
+    def _allreduce_critic_grads(self) -> None:
+        super()._allreduce_critic_grads()
+        # context_group exists exactly for original CARE: the modified
+        # contextEncoder is one frozen embedding, the original one always
+        # has its trainable embedding header (_build_optimizers keeps
+        # the requires_grad parameters)
+        if self.ddp is not None and self.context_group is not None:
+            self.ddp.allreduce_grad_(self.context_group.flat_grad)
 
     @torch.no_grad()
     def _manual_seg1(self, batch):
+        """CARE's segment 1, both variants (CARE(M) frozen context,
+        original CARE trainable context encoder): z_context, one batched
+        state-encoder forward under the actor head, the target state
+        encoder under the TD heads, and after the critic chain backward
+        the state-encoder (and context) backward: critic and context
+        gradients.  Reference gradient-flow rules
+        (MT10_Distributed_CARE/src/learner.py:281-404): trunk input
+        detached, the actor optimizes only its head, context gradients
+        come from the critic loss only."""
         from ..ops import native
         ext = native()
-        states, actions = batch["states"], batch["actions"]
-        rewards, next_states, dones = (batch["rewards"],
-                                       batch["next_states"], batch["dones"])
+        states, next_states = batch["states"], batch["next_states"]
         T = self.num_tasks
-        use_w = self.use_weighted_loss
         B = states.shape[0]
-        A = self.actor.action_dim
-        la_det = self.log_alpha.detach()
         sd = states.shape[1] - T                 # raw state dim
-        D = self._se_local["mixW"][-1].shape[2]
         info = self._se_local
         orig = not self.use_modified_care
         # ONE launch re-packs every pre-step weight set
@@ -705,21 +677,7 @@ class CAREEngine(SACEngine):
 
         # ---- batched actor head + squash ------------------------------
         out, acts_a = self._actor_chain.forward(enc_cat)
-        mu, lsr = out[:, :A], out[:, A:]
-        krng = self._use_krng and not self._eps_queue
-        if self._eps_queue:
-            eps = torch.cat([self._next_eps(mu[:B]), self._next_eps(mu[:B])])
-        elif krng:
-            # eps GENERATED inside the squash kernel (counter RNG) and
-            # written here for the backward — no randn launch
-            eps = torch.empty(mu.shape, device=mu.device, dtype=mu.dtype)
-        else:
-            eps = torch.randn_like(mu)
-        a_cat, lp_cat, tanh_u, ls_cat = ext.squashed_gaussian_fwd(
-            mu, lsr, eps, float(self.actor.k),
-            self._rng_ctr if krng else None)
-        na, nlp = a_cat[:B], lp_cat[:B]
-        sa, lp = a_cat[B:], lp_cat[B:]
+        a_cat, lp_cat, tanh_u, ls_cat, lsr, eps = self._squash_cat(out, B)
 
         # ---- TD target (target SE + target heads, no grad) ------------
         enc_t, _ = self._se_fwd_manual(self._se_target,
@@ -727,16 +685,12 @@ class CAREEngine(SACEngine):
                                        zc16)
         # target heads + critic heads: independent chains, ONE launch
         ((q1_t, q2_t), _), ((q1, q2), acts_q) = forward_pair(
-            (self._target_chain, (enc_t, na), {"save_acts": False}),
-            (self._critic_chain, (enc_cat[B:], actions), {}))
-        y = ext.td_target_mt(rewards, dones, q1_t, q2_t, nlp, states,
-                             la_det, T, self.gamma, self.reward_scale)
+            (self._target_chain, (enc_t, a_cat[:B]), {"save_acts": False}),
+            (self._critic_chain, (enc_cat[B:], batch["actions"]), {}))
 
         # ---- critic loss + manual backward ----------------------------
-        closs = ext.critic_loss_fwd(q1, q2, y, states, la_det, T,
-                                    int(use_w), self._loss_ws)[0]
-        dy = ext.critic_loss_bwd2(q1, q2, y, states, la_det, closs, T,
-                                  int(use_w))
+        closs, dy = self._critic_loss_step(batch, q1_t, q2_t, lp_cat[:B],
+                                           q1, q2)
         fg_c = self.critic_group.flat_grad
         arena_c, S_c, ch_c = self._dw_arena("critic",
                                             self.critic_group.numel, B)
@@ -827,76 +781,38 @@ class CAREEngine(SACEngine):
                                      arena_x, S_x, ch_x)
             ext.reduce_arena(arena_x, self.context_group.flat_grad, S_x)
         self._dp_st = dict(
-            states=states, sd=sd, zc16=zc16, sa=sa, lp=lp,
+            states=states, sd=sd, zc16=zc16, sa=a_cat[B:], lp=lp_cat[B:],
             ls_cat=ls_cat, B=B, eps=eps, tanh_u=tanh_u, lsr=lsr,
-            acts_a=acts_a, la_det=la_det,
-            T=T, use_w=use_w, closs=closs, orig=orig)
+            acts_a=acts_a, closs=closs)
 
     @torch.no_grad()
     def _manual_seg2(self):
+        """CARE's head of segment 2: the actor step's critic-side encoding
+        comes from the POST-step state encoder."""
         from ..ops import native
-        ext = native()
         st = self._dp_st
-        states, sd, zc16 = st["states"], st["sd"], st["zc16"]
-        sa, lp, ls_cat, B = st["sa"], st["lp"], st["ls_cat"], st["B"]
-        eps, tanh_u, lsr = st["eps"], st["tanh_u"], st["lsr"]
-        la_det, T, use_w = st["la_det"], st["T"], st["use_w"]
-        info = self._se_local
         st["prolog"] = self._adam_prolog_all()
         # adam kernel refreshes the flat bf16 mirror
         self.critic_optimizer.step(pre_prologed=st["prolog"])
         self._refresh_mixT("critic")   # transposed mixture views still need it
-
-        # ---- actor/alpha loss + manual backward -----------------------
-        enc_c, _ = self._se_fwd_manual(info, states[:, :sd].to(torch.bfloat16),
-                                       zc16)               # post-step SE
+        enc_c, _ = self._se_fwd_manual(
+            self._se_local, st["states"][:, :st["sd"]].to(torch.bfloat16),
+            st["zc16"])
         # re-pack the POST-Adam critic (fwd + dx) in one launch
-        pack_chains(ext, [(self._critic_chain, True, True)])
-        (aq1, aq2), acts_f = self._critic_chain.forward(enc_c, sa)
-        # fwd kernel zeroes the alpha flat grad in passing (bwd atomics
-        # target) — no separate fill launch
-        al = ext.actor_alpha_loss_fwd(aq1, aq2, lp, ls_cat[B:], states,
-                                      la_det, T, int(use_w), self.H_bar_f,
-                                      self.alpha_group.flat_grad,
-                                      self._aloss_ws)
-        daq, dlp = ext.actor_alpha_loss_bwd2(
-            aq1, aq2, lp, states, la_det, al, self.alpha_group.flat_grad,
-            T, int(use_w), self.H_bar_f, self._dla_ws)
-        # dQ/d(action) only; twin heads summed inside squash bwd2
-        dsa = self._critic_chain.input_grad(daq, acts_f, enc_c.shape[1])
-        dhead = ext.squashed_gaussian_bwd2(
-            dsa, dlp, lsr[B:], ls_cat[B:], eps[B:], tanh_u[B:],
-            float(self.actor.k))
-        fg_a = self.actor_group.flat_grad
-        arena_a, S_a, ch_a = self._dw_arena("actor",
-                                            self.actor_group.numel, B)
-        self._actor_chain.backward(dhead, st["acts_a"], arena_a, S_a, ch_a,
-                                   rows=slice(B, None))
-        ext.reduce_arena(arena_a, fg_a, S_a)
-        st["al"] = al
+        pack_chains(native(), [(self._critic_chain, True, True)])
+        (aq1, aq2), acts_f = self._critic_chain.forward(enc_c, st["sa"])
+        self._actor_alpha_backward(aq1, aq2, acts_f, enc_c.shape[1])
 
-    @torch.no_grad()
-    def _manual_seg3(self):
-        st = self._dp_st
-        FusedAdam.step_many(
-            [self.actor_optimizer, self.log_alpha_optimizer],
-            rng_bump=(None if st.get("prolog")
-                      else (self._rng_ctr if self._use_krng else None)),
-            pre_prologed=bool(st.get("prolog")))
-        # self.alpha refreshed lazily outside the graph (see SACEngine)
+    def _update_targets(self) -> None:
+        """Two-tau Polyak, then what CARE's update ends with: the context
+        Adam (its gradient came from the critic backward; it refreshes the
+        context mirror, its prolog ran in seg2) and the encoder tie."""
         self._polyak_targets(mirror=self._target_bf16)
         self._refresh_mixT("target")
-        if st["orig"]:
-            # refreshes ctx mirror; prolog already ran in seg2
+        if self.context_encoder_optimizer is not None:
             self.context_encoder_optimizer.step(
-                pre_prologed=bool(st.get("prolog")))
+                pre_prologed=self._dp_st["prolog"])
         self.tie_actor_state_encoder()
-        closs, al = st["closs"], st["al"]
-        return self._clip_metrics({
-            "critic_loss": closs[6],  # summed in-kernel
-            "actor_loss": al[0],
-            "alpha_loss": al[2],
-            "entropy": al[3]})
 
     @torch.no_grad()
     def publish_params(self) -> torch.Tensor:

@@ -69,6 +69,17 @@ class SACEngine:
         self.per_indices: Optional[torch.Tensor] = None
         self.per_new_priorities: Optional[torch.Tensor] = None
         self._per_zeroed = False
+        # optional state: the bf16 / CARE / capture setup below fills in
+        # what its path has, every reader sees a plain attribute
+        self._bf16 = False
+        self._se_fast = False
+        self._rng_ctr: Optional[torch.Tensor] = None
+        self._target_bf16: Optional[torch.Tensor] = None
+        self._ctx_chain = None
+        self._dw_arenas: dict = {}
+        self._graph_chunk = 1
+        self._dp_graphs = None
+        self.context_encoder_optimizer = None
         self._build_models()
         self._build_optimizers()
         self._init_grad_clip(max_grad_norm)
@@ -92,7 +103,7 @@ class SACEngine:
         self.actor_optimizer.set_max_grad_norm(c, self._grad_skips)
         self.log_alpha_optimizer.set_max_grad_norm(float("inf"),
                                                    self._grad_skips)
-        ctx = getattr(self, "context_encoder_optimizer", None)
+        ctx = self.context_encoder_optimizer
         if ctx is not None:
             ctx.set_max_grad_norm(c, self._grad_skips)
 
@@ -104,7 +115,7 @@ class SACEngine:
             return out
         out["critic_grad_norm"] = self.critic_optimizer.grad_norm
         out["actor_grad_norm"] = self.actor_optimizer.grad_norm
-        ctx = getattr(self, "context_encoder_optimizer", None)
+        ctx = self.context_encoder_optimizer
         if ctx is not None:
             out["context_grad_norm"] = ctx.grad_norm
         out["grad_skips"] = self._grad_skips[0]
@@ -114,6 +125,17 @@ class SACEngine:
         if self._eps_queue:
             return self._eps_queue.pop(0).to(like.device)
         return torch.randn_like(like)
+
+    def _eps_cat(self, mu: torch.Tensor, B: int,
+                 in_kernel: bool = False) -> torch.Tensor:
+        """eps for the batched [next | current] actor pass ``mu [2B, A]``:
+        two queued draws (test hook), else storage the squash kernel fills
+        from the counter RNG (``in_kernel``), else one randn launch."""
+        if self._eps_queue:
+            return torch.cat([self._next_eps(mu[:B]), self._next_eps(mu[:B])])
+        if in_kernel:
+            return torch.empty(mu.shape, device=mu.device, dtype=mu.dtype)
+        return torch.randn_like(mu)
 
     def _sample(self, states: torch.Tensor):
         """Actor sampling with squashed-Gaussian op (both actor families)."""
@@ -329,7 +351,7 @@ class SACEngine:
 
     @torch.no_grad()
     def refresh_bf16(self, which: str = "all") -> None:
-        if not getattr(self, "_bf16", False):
+        if not self._bf16:
             return
         if which in ("all", "critic"):
             self._critic_bf16.copy_(self.critic_group.flat_data)
@@ -378,7 +400,7 @@ class SACEngine:
     def _critic_q(self, states, actions):
         if self._use_fused(states):
             x = torch.cat([states, actions], dim=-1)
-            if getattr(self, "_bf16", False):
+            if self._bf16:
                 return Fops.twin_mlp_forward_bf16(x, *self._twin_local,
                                                   self._twin_local_bf16)
             return Fops.twin_mlp_forward(x, *self._twin_local)
@@ -390,7 +412,7 @@ class SACEngine:
     def _target_q(self, states, actions):
         if self._use_fused(states):
             x = torch.cat([states, actions], dim=-1)
-            if getattr(self, "_bf16", False):
+            if self._bf16:
                 return Fops.twin_mlp_forward_bf16(x, *self._twin_target,
                                                   self._target_chain.ws16)
             return Fops.twin_mlp_forward(x, *self._twin_target)
@@ -418,7 +440,7 @@ class SACEngine:
             why = "not defined for weighted_loss_mode='reference'"
         elif self.device.type == "cuda" and self._use_fused(
                 self.log_alpha) and not (
-                getattr(self, "_bf16", False)
+                self._bf16
                 and os.environ.get("DSAC_NO_MANUAL", "0") != "1"):
             why = ("on a GPU only the bf16 manual-backward path carries "
                    "importance-sampling weights (not the fp32 fused path)")
@@ -597,9 +619,7 @@ class SACEngine:
         k_reduce_arena launch folds the whole phase's gradient (instead of
         one reduce per layer).  chunk targets ~8 batch splits, rounded to
         the 64-row GEMM tile."""
-        store = getattr(self, "_dw_arenas", None)
-        if store is None:
-            store = self._dw_arenas = {}
+        store = self._dw_arenas
         key = (name, numel, B)
         if key not in store:
             if name.endswith("@rowblocks"):
@@ -628,15 +648,24 @@ class SACEngine:
         between replays — see :meth:`capture_dp`:
           seg1: forwards + TD target + critic backward  -> critic grad
           seg2: critic Adam + actor/alpha forwards+backwards -> aa grads
-          seg3: actor+alpha fused Adam + Polyak
+          seg3: actor+alpha fused Adam + target update
+        Both engines run this sequence.  The segments hand their state on
+        in the plain dict ``_dp_st``; each sets every key the next reads.
+        :class:`CAREEngine` has its own seg1 and seg2 head (encoders) and
+        shares the steps: :meth:`_squash_cat`, :meth:`_critic_loss_step`,
+        :meth:`_actor_alpha_backward`, seg3 with :meth:`_update_targets`.
         """
         self._manual_seg1(batch)
-        if self.ddp is not None:
-            self.ddp.allreduce_grad_(self.critic_group.flat_grad)
+        self._allreduce_critic_grads()
         self._manual_seg2()
         if self.ddp is not None:
             self.ddp.allreduce_grad_(self._aa_arena)
         return self._manual_seg3()
+
+    def _allreduce_critic_grads(self) -> None:
+        """The collectives due between the critic backward and its Adam."""
+        if self.ddp is not None:
+            self.ddp.allreduce_grad_(self.critic_group.flat_grad)
 
     @property
     def _use_krng(self) -> bool:
@@ -644,8 +673,8 @@ class SACEngine:
         kernels (round 2): replaces the torch rand+randn launches and the
         hipGraph RNG-offset bookkeeping kernels.  DSAC_KRNG=0 restores
         torch's philox draws."""
-        return (getattr(self, "_bf16", False)
-                and getattr(self, "_rng_ctr", None) is not None
+        return (self._bf16
+                and self._rng_ctr is not None
                 and os.environ.get("DSAC_KRNG", "1") == "1")
 
     @property
@@ -666,7 +695,7 @@ class SACEngine:
         from ..ops import native
         opts = [self.critic_optimizer, self.actor_optimizer,
                 self.log_alpha_optimizer]
-        ctx = getattr(self, "context_encoder_optimizer", None)
+        ctx = self.context_encoder_optimizer
         if ctx is not None:
             opts.append(ctx)
         if any(o._dev_state is None for o in opts):
@@ -686,16 +715,8 @@ class SACEngine:
         for all-reduce."""
         from ..ops import native
         ext = native()
-        states = batch["states"]
-        actions = batch["actions"]
-        rewards = batch["rewards"]
-        next_states = batch["next_states"]
-        dones = batch["dones"]
-        T = self.num_tasks
-        use_w = self.use_weighted_loss
+        states, next_states = batch["states"], batch["next_states"]
         B = states.shape[0]
-        A = self.cfg.action_dim
-        la_det = self.log_alpha.detach()
         # ONE launch re-packs every pre-step weight set into the
         # fragment layout (critic fwd+dx, target fwd, actor fwd+dx)
         pack_chains(ext, [(self._critic_chain, True, True),
@@ -705,35 +726,65 @@ class SACEngine:
         # ---- batched actor forward + squash --------------------------
         out, acts_a = self._actor_chain.forward(next_states, states,
                                                 rowcat=True)
-        mu, lsr = out[:, :A], out[:, A:]
-        krng = self._use_krng and not self._eps_queue
-        if self._eps_queue:
-            eps = torch.cat([self._next_eps(mu[:B]), self._next_eps(mu[:B])])
-        elif krng:
-            # eps GENERATED inside the squash kernel (counter RNG) and
-            # written here for the backward — no randn launch
-            eps = torch.empty(mu.shape, device=mu.device, dtype=mu.dtype)
-        else:
-            eps = torch.randn_like(mu)
-        a_cat, lp_cat, tanh_u, ls_cat = ext.squashed_gaussian_fwd(
-            mu, lsr, eps, float(self.actor.k),
-            self._rng_ctr if krng else None)
-        na, nlp = a_cat[:B], lp_cat[:B]
+        a_cat, lp_cat, tanh_u, ls_cat, lsr, eps = self._squash_cat(out, B)
 
         # ---- TD-target twin + critic twin: independent chains of one
         # shape, ONE launch (each alone fills 160 of 256 CUs) ------------
         ((q1_t, q2_t), _), ((q1, q2), acts_c) = forward_pair(
-            (self._target_chain, (next_states, na), {"save_acts": False}),
-            (self._critic_chain, (states, actions), {}))
-        fuse = self._fuse_tail
+            (self._target_chain, (next_states, a_cat[:B]),
+             {"save_acts": False}),
+            (self._critic_chain, (states, batch["actions"]), {}))
+        closs, dy = self._critic_loss_step(batch, q1_t, q2_t, lp_cat[:B],
+                                           q1, q2)
+        arena_c, S_c, ch_c = self._dw_arena("critic",
+                                            self.critic_group.numel, B)
+        self._critic_chain.backward(dy, acts_c, arena_c, S_c, ch_c)
+        # single-GPU: the critic Adam kernel folds the arena itself; with
+        # DP the all-reduce needs the folded gradient first
+        fold_c = self._fuse_tail and self.ddp is None
+        if not fold_c:
+            ext.reduce_arena(arena_c, self.critic_group.flat_grad, S_c)
+        self._dp_st = {
+            "arena_c": (arena_c, S_c) if fold_c else None,
+            "states": states, "sa": a_cat[B:], "lp": lp_cat[B:],
+            "lsr": lsr, "ls_cat": ls_cat, "eps": eps, "tanh_u": tanh_u,
+            "acts_a": acts_a, "closs": closs, "B": B,
+        }
+
+    def _squash_cat(self, out: torch.Tensor, B: int):
+        """Squash the batched [next | current] actor output ``[2B, 2A]``
+        (mu | raw log-std, read in place).  Returns ``a_cat, lp_cat,
+        tanh_u, ls_cat, lsr, eps``: rows ``[:B]`` feed the TD target, rows
+        ``[B:]`` the actor step and its backward."""
+        from ..ops import native
+        A = out.shape[1] // 2
+        mu, lsr = out[:, :A], out[:, A:]
+        # eps GENERATED inside the squash kernel (counter RNG) and written
+        # out for the backward — no randn launch
+        krng = self._use_krng and not self._eps_queue
+        eps = self._eps_cat(mu, B, in_kernel=krng)
+        a_cat, lp_cat, tanh_u, ls_cat = native().squashed_gaussian_fwd(
+            mu, lsr, eps, float(self.actor.k),
+            self._rng_ctr if krng else None)
+        return a_cat, lp_cat, tanh_u, ls_cat, lsr, eps
+
+    def _critic_loss_step(self, batch, q1_t, q2_t, nlp, q1, q2):
+        """TD target + critic loss forward + backward on the four twin
+        heads.  Returns ``closs`` (the loss kernel's metric slots) and
+        ``dy``, the bf16 gradient at the critic heads."""
+        from ..ops import native
+        ext = native()
+        states, rewards, dones = (batch["states"], batch["rewards"],
+                                  batch["dones"])
+        T = self.num_tasks
+        use_w = self.use_weighted_loss
+        la_det = self.log_alpha.detach()
         # one launch for TD target + loss fwd + dq (its grid covers the
         # batch in <= 32 blocks); a larger batch keeps the three launches
-        fuse_loss = fuse and B <= 8192
+        fuse_loss = self._fuse_tail and states.shape[0] <= 8192
         if not fuse_loss:
             y = ext.td_target_mt(rewards, dones, q1_t, q2_t, nlp, states,
                                  la_det, T, self.gamma, self.reward_scale)
-
-        # ---- critic loss + manual backward ---------------------------
         if "is_weights" in batch:
             if not fuse_loss:
                 raise NotImplementedError(
@@ -759,21 +810,7 @@ class SACEngine:
                                         int(use_w), self._loss_ws)[0]
             dy = ext.critic_loss_bwd2(q1, q2, y, states, la_det, closs, T,
                                       int(use_w))
-        fg_c = self.critic_group.flat_grad
-        arena_c, S_c, ch_c = self._dw_arena("critic",
-                                            self.critic_group.numel, B)
-        self._critic_chain.backward(dy, acts_c, arena_c, S_c, ch_c)
-        # single-GPU: the critic Adam kernel folds the arena itself; with
-        # DP the all-reduce needs the folded gradient first
-        fold_c = fuse and self.ddp is None
-        if not fold_c:
-            ext.reduce_arena(arena_c, fg_c, S_c)
-        self._dp_st = {
-            "fuse": fuse, "arena_c": (arena_c, S_c) if fold_c else None,
-            "states": states, "sa": a_cat[B:], "lp": lp_cat[B:],
-            "lsr": lsr, "ls_cat": ls_cat, "eps": eps, "tanh_u": tanh_u,
-            "acts_a": acts_a, "la_det": la_det, "closs": closs, "B": B,
-        }
+        return closs, dy
 
     @torch.no_grad()
     def _manual_seg2(self):
@@ -782,26 +819,35 @@ class SACEngine:
         manual backward.  Ends with the fused actor+alpha gradient arena
         ready for all-reduce."""
         from ..ops import native
-        ext = native()
         st = self._dp_st
         st["prolog"] = self._adam_prolog_all()
         # adam kernel also refreshes the bf16 mirror
         self.critic_optimizer.step(pre_prologed=st["prolog"],
                                    arena=st["arena_c"])
+        # re-pack the POST-Adam critic (fwd + dx) in one launch
+        pack_chains(native(), [(self._critic_chain, True, True)])
+        states = st["states"]
+        (aq1, aq2), acts_f = self._critic_chain.forward(states, st["sa"])
+        self._actor_alpha_backward(aq1, aq2, acts_f, states.shape[1])
 
-        states, sa, lp = st["states"], st["sa"], st["lp"]
-        B = st["B"]
+    def _actor_alpha_backward(self, aq1, aq2, acts_f, lo: int) -> None:
+        """Seg2 from the loss kernels on: actor/alpha losses on the
+        post-step twin ``aq1, aq2``, dQ/d(action) back through the critic
+        chain (``lo``: width of its first input, which takes no gradient),
+        squash backward, actor chain backward on the current-state rows.
+        Leaves ``st["al"]`` (metric slots) and ``st["arena_a"]`` (the
+        actor split-K arena for seg3 to fold, or None once folded)."""
+        from ..ops import native
+        ext = native()
+        st = self._dp_st
+        states, lp, B = st["states"], st["lp"], st["B"]
         T = self.num_tasks
         use_w = self.use_weighted_loss
-        la_det = st["la_det"]
+        la_det = self.log_alpha.detach()
         ls = st["ls_cat"][B:]
-
-        # re-pack the POST-Adam critic (fwd + dx) in one launch
-        pack_chains(ext, [(self._critic_chain, True, True)])
-        (aq1, aq2), acts_f = self._critic_chain.forward(states, sa)
+        fuse = self._fuse_tail
         # the fwd kernel zeroes the alpha flat grad in passing (the bwd's
         # atomics target) — no separate fill launch
-        fuse = st["fuse"]
         if fuse and B <= 8192:
             # forward metrics, dq/dlp and the alpha flat grad in one launch.
             # The weighted-loss normalizer is the one the critic loss of
@@ -823,7 +869,7 @@ class SACEngine:
                 self._dla_ws)
         # dQ/d(action) only ([2, B, A] fp32 on the chain kernels); the twin
         # heads are summed inside squash bwd2
-        dsa = self._critic_chain.input_grad(daq, acts_f, states.shape[1])
+        dsa = self._critic_chain.input_grad(daq, acts_f, lo)
         dhead = ext.squashed_gaussian_bwd2(
             dsa, dlp, st["lsr"][B:], st["ls_cat"][B:], st["eps"][B:],
             st["tanh_u"][B:], float(self.actor.k))
@@ -840,26 +886,21 @@ class SACEngine:
 
     @torch.no_grad()
     def _manual_seg3(self):
-        """Segment 3: fused actor+alpha Adam, Polyak target update."""
+        """Segment 3: fused actor+alpha Adam, then the target side
+        (:meth:`_update_targets`)."""
         st = self._dp_st
-        polyak = (self.target_group, self.critic_group, self.tau,
-                  getattr(self, "_target_bf16", None))
-        fuse = bool(st.get("fuse"))
         # fused tail: the same launch folds the actor split-K arena and
         # does the Polyak update (it reads the critic stepped in seg2)
-        FusedAdam.step_many([self.actor_optimizer,
-                             self.log_alpha_optimizer],
-                            rng_bump=(None if st.get("prolog")
-                                      else (self._rng_ctr if self._use_krng
-                                            else None)),
-                            pre_prologed=bool(st.get("prolog")),
-                            arena0=st.get("arena_a"),
-                            polyak=polyak if fuse else None)
+        FusedAdam.step_many(
+            [self.actor_optimizer, self.log_alpha_optimizer],
+            rng_bump=(None if st["prolog"]
+                      else (self._rng_ctr if self._use_krng else None)),
+            pre_prologed=st["prolog"], arena0=st["arena_a"],
+            polyak=self._polyak_args() if self._fuse_tail else None)
         # NOTE: self.alpha is refreshed lazily (checkpoint/_per_sample_alpha
         # recompute from log_alpha) — an exp() here would replay as a
         # ~5 µs kernel every captured step just for bookkeeping
-        if not fuse:
-            flat_polyak_(*polyak)
+        self._update_targets()
         closs, al = st["closs"], st["al"]
         return self._clip_metrics({
             "critic_loss": closs[6],  # summed in-kernel
@@ -867,6 +908,16 @@ class SACEngine:
             "alpha_loss": al[2],
             "entropy": al[3],
         })
+
+    def _polyak_args(self):
+        return (self.target_group, self.critic_group, self.tau,
+                self._target_bf16)
+
+    def _update_targets(self) -> None:
+        """What seg3 does after the actor+alpha Adam: the Polyak update,
+        unless the fused tail did it inside that launch."""
+        if not self._fuse_tail:
+            flat_polyak_(*self._polyak_args())
 
     def _update_tensors_fused(self, batch):
         """GPU path: same math/order as update_tensors, restructured for
@@ -891,7 +942,7 @@ class SACEngine:
         B = states.shape[0]
         A = self.cfg.action_dim
 
-        if getattr(self, "_bf16", False) \
+        if self._bf16 \
                 and os.environ.get("DSAC_NO_MANUAL", "0") != "1":
             return self._update_tensors_manual(batch)
         self.zero_grad()
@@ -903,18 +954,14 @@ class SACEngine:
         # profiles/r04_NOTES.md), so the TD block stays on the main stream.
         x_cat = torch.cat([next_states, states], dim=0)
         ws, bs = self._actor_weights()
-        if getattr(self, "_bf16", False):
+        if self._bf16:
             out = Fops.mlp_forward_bf16(x_cat, ws, bs, self._actor_ws_bf16,
                                         grad_row_start=B)
         else:
             out = Fops.mlp_forward(x_cat, ws, bs, grad_row_start=B)
         mu, lsr = out[:, :A], out[:, A:]
-        if self._eps_queue:
-            eps = torch.cat([self._next_eps(mu[:B]), self._next_eps(mu[:B])])
-        else:
-            eps = torch.randn_like(mu)
-        a_cat, lp_cat, ls_cat = Fops.squashed_gaussian(mu, lsr, eps,
-                                                       self.actor.k)
+        a_cat, lp_cat, ls_cat = Fops.squashed_gaussian(
+            mu, lsr, self._eps_cat(mu, B), self.actor.k)
         next_actions = a_cat[:B].detach()
         next_log_probs = lp_cat[:B].detach()
         sampled_actions = a_cat[B:]
@@ -931,14 +978,13 @@ class SACEngine:
                                   T, use_w)
         q_loss = l1 + l2
         q_loss.backward()
-        if self.ddp is not None:
-            self.ddp.allreduce_grad_(self.critic_group.flat_grad)
+        self._allreduce_critic_grads()
         self.critic_optimizer.step()
         self.refresh_bf16("critic")
 
         # --- actor/alpha step (post-critic-step critic, frozen heads) --
         xa = torch.cat([states, sampled_actions], dim=-1)
-        if getattr(self, "_bf16", False):
+        if self._bf16:
             aq1, aq2 = Fops.twin_mlp_forward_bf16(xa,
                                                   *self._twin_local_frozen,
                                                   self._twin_local_bf16)
@@ -955,7 +1001,7 @@ class SACEngine:
         self.alpha = self.log_alpha.exp().detach()
 
         flat_polyak_(self.target_group, self.critic_group, self.tau,
-                     mirror=getattr(self, "_target_bf16", None))
+                     mirror=self._target_bf16)
         return self._clip_metrics({
             "critic_loss": q_loss.detach(),
             "actor_loss": policy_loss.detach(),
@@ -1005,7 +1051,7 @@ class SACEngine:
         """Replay the captured chunk (tensor metrics refresh in place);
         advances ``update_iteration`` by the captured chunk size."""
         self._graph.replay()
-        self.update_iteration += getattr(self, "_graph_chunk", 1)
+        self.update_iteration += self._graph_chunk
         return self._graph_metrics
 
     # ------------------------------------------------------------------
@@ -1027,7 +1073,7 @@ class SACEngine:
         if self._use_krng and hasattr(replay, "attach_rng"):
             replay.attach_rng(self._rng_ctr)
         assert self.device.type == "cuda", "capture needs a GPU"
-        assert getattr(self, "_bf16", False), \
+        assert self._bf16, \
             "segmented DP capture runs the bf16 manual-backward path"
         torch.cuda.synchronize(self.device)
         side = torch.cuda.Stream(self.device)
@@ -1056,8 +1102,7 @@ class SACEngine:
         """Replay the segmented DP update with eager RCCL between."""
         g1, g2, g3 = self._dp_graphs
         g1.replay()
-        if self.ddp is not None:
-            self.ddp.allreduce_grad_(self.critic_group.flat_grad)
+        self._allreduce_critic_grads()
         g2.replay()
         if self.ddp is not None:
             self.ddp.allreduce_grad_(self._aa_arena)

@@ -233,3 +233,68 @@ def test_chain_switch_equivalence(case, tmp_path, monkeypatch):
     for n, g in _groups(fresh).items():
         assert not torch.equal(g.flat_data, g1[n].flat_data), n
         assert not torch.equal(g.flat_data, g0[n].flat_data), n
+
+
+class _RecordingDP:
+    """Stands in for a DataParallelGroup and records what is all-reduced.
+    A world-1 group cannot show a missing collective (its all-reduce is
+    the identity); the recorded order of buffers can."""
+    enabled = True
+    world_size = 1
+
+    def __init__(self):
+        self.ptrs = []
+
+    def broadcast_params(self, t):
+        pass
+
+    def allreduce_grad_(self, t):
+        self.ptrs.append(t.data_ptr())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["mtsac", "care_m", "care_orig"])
+def test_allreduce_sequence(case, tmp_path):
+    """One update all-reduces exactly [critic flat grad, actor+alpha
+    arena], original CARE the context flat grad between the two: eagerly
+    and through the segmented data-parallel graphs."""
+    from tests.test_engine import make_batch
+    from distributed_sac_amd.replay import ShardedReplay
+    torch.manual_seed(0)
+    e, cfg = _engine(case, tmp_path)
+    dp = _RecordingDP()
+    e.attach_ddp(dp)
+    ctx = _groups(e).get("context")
+    assert (ctx is not None) == (case == "care_orig")
+    # the actor group's gradient opens the shared actor+alpha arena
+    want = [e.critic_group.flat_grad.data_ptr()]
+    if ctx is not None:
+        want.append(ctx.flat_grad.data_ptr())
+    want.append(e.actor_group.flat_grad.data_ptr())
+    assert len(set(want)) == len(want)
+    assert (e.alpha_group.flat_grad.data_ptr()
+            == want[-1] + 4 * e.actor_group.numel)
+
+    batch = {k: v.cuda() for k, v in
+             make_batch(cfg, cfg.batch_size, seed=0).items()}
+    e.update_tensors(batch)
+    assert dp.ptrs == want
+
+    T = cfg.num_tasks
+    replay = ShardedReplay(4096, T, cfg.mtobs_dim, cfg.action_dim,
+                           device="cuda:0", seed=3)
+    for tsk in range(T):
+        n = 256
+        s = torch.randn(n, cfg.mtobs_dim, device="cuda")
+        s[:, -T:] = 0
+        s[:, -T + tsk] = 1
+        replay.shards[tsk].append(
+            s, torch.rand(n, cfg.action_dim, device="cuda") * 2 - 1,
+            torch.randn(n, 1, device="cuda"), s.clone(),
+            torch.zeros(n, 1, device="cuda"))
+    e.capture_dp(replay, cfg.batch_size)
+    del dp.ptrs[:]
+    m = e.dp_graphed_update()
+    torch.cuda.synchronize()
+    assert dp.ptrs == want
+    assert all(bool(torch.isfinite(v)) for v in m.values())
