@@ -105,10 +105,17 @@ class ShmRing {
     if (owner_) shm_unlink(name_.c_str());
   }
 
+  // Best effort: drains memcpy out of the ring, so an unregistered ring
+  // works all the same.  Where the platform cannot register mapped memory
+  // the call fails, and its error has to be consumed here — HIP keeps it
+  // as the thread's last error, and the next kernel launch's check would
+  // report it as its own.
   void pin() {
-    if (!pinned_ && hipHostRegister(base_, size_, hipHostRegisterDefault)
-                        == hipSuccess) {
+    if (pinned_) return;
+    if (hipHostRegister(base_, size_, hipHostRegisterDefault) == hipSuccess) {
       pinned_ = true;
+    } else {
+      (void)hipGetLastError();
     }
   }
 

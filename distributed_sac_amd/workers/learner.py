@@ -96,7 +96,7 @@ class Learner:
         self.ingest = ingest
         if self.rings and self.device.type == "cuda":
             for r in self.rings:
-                r.pin()  # hipHostRegister: DMA-able drains
+                r.pin()  # hipHostRegister where the platform can
         self.log_queue = log_queue
         self.logger = logger or MetricLogger(None)
         self.save_dir = save_dir
