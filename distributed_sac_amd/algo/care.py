@@ -363,8 +363,13 @@ class CAREEngine(SACEngine):
             zc = z_context
         return torch.cat([zc, z_enc], dim=1)
 
-    def _twin_fwd(self, x, which: str):
+    def _twin_fwd(self, x, which: str, x2=None):
+        """x2: the heads' input is [x || x2].  fp32 hands both to
+        twin_mlp_forward (torch.cat, or with DSAC_F32_CHAIN=1 the chain
+        kernel's loader); bf16 concatenates here."""
         if self._bf16:
+            if x2 is not None:
+                x = torch.cat([x, x2], dim=-1)
             if which == "target":
                 return Fops.twin_mlp_forward_bf16(x, *self._twin_target,
                                                   self._target_chain.ws16)
@@ -375,10 +380,10 @@ class CAREEngine(SACEngine):
             return Fops.twin_mlp_forward_bf16(x, *self._twin_local,
                                               self._twin_local_bf16)
         if which == "target":
-            return Fops.twin_mlp_forward(x, *self._twin_target)
+            return Fops.twin_mlp_forward(x, *self._twin_target, x2=x2)
         if which == "frozen":
-            return Fops.twin_mlp_forward(x, *self._twin_local_frozen)
-        return Fops.twin_mlp_forward(x, *self._twin_local)
+            return Fops.twin_mlp_forward(x, *self._twin_local_frozen, x2=x2)
+        return Fops.twin_mlp_forward(x, *self._twin_local, x2=x2)
 
     def _update_tensors_fused(self, batch):
         """GPU path: fused losses + twin-head grouped GEMMs (bf16 mirrors
@@ -440,8 +445,7 @@ class CAREEngine(SACEngine):
                                           z_context)
             else:
                 enc_t = self.target_critic.encode(next_states, z_context)
-            xt = torch.cat([enc_t, na], dim=-1)
-            q1_t, q2_t = self._twin_fwd(xt, "target")
+            q1_t, q2_t = self._twin_fwd(enc_t, "target", x2=na)
             y = native().td_target_mt(rewards, dones, q1_t, q2_t, nlp,
                                       states, self.log_alpha.detach(), T,
                                       self.gamma, self.reward_scale)
@@ -450,8 +454,7 @@ class CAREEngine(SACEngine):
             enc = enc_cat[B:]
         else:
             enc = self.local_critic.encode(states, z_context)
-        x = torch.cat([enc, actions], dim=-1)
-        q1, q2 = self._twin_fwd(x, "local")
+        q1, q2 = self._twin_fwd(enc, "local", x2=actions)
         l1, l2 = Fops.critic_loss(q1, q2, y, states, self.log_alpha.detach(),
                                   T, use_w)
         q_loss = l1 + l2
@@ -466,8 +469,7 @@ class CAREEngine(SACEngine):
             else:
                 enc_c = self.local_critic.encode(states, zc_d,
                                                  detach_z_encs=True)
-        xa = torch.cat([enc_c, sa], dim=-1)
-        aq1, aq2 = self._twin_fwd(xa, "frozen")
+        aq1, aq2 = self._twin_fwd(enc_c, "frozen", x2=sa)
         policy_loss, loss_log_alpha, entropy = Fops.actor_alpha_loss(
             aq1, aq2, lp, ls, states, self.log_alpha, T, use_w, self.H_bar_f)
         (policy_loss + loss_log_alpha).backward()

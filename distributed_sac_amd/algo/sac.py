@@ -399,11 +399,14 @@ class SACEngine:
 
     def _critic_q(self, states, actions):
         if self._use_fused(states):
-            x = torch.cat([states, actions], dim=-1)
             if self._bf16:
+                x = torch.cat([states, actions], dim=-1)
                 return Fops.twin_mlp_forward_bf16(x, *self._twin_local,
                                                   self._twin_local_bf16)
-            return Fops.twin_mlp_forward(x, *self._twin_local)
+            # x2: concatenated by torch.cat, or, with DSAC_F32_CHAIN=1, in
+            # the chain kernel's loader
+            return Fops.twin_mlp_forward(states, *self._twin_local,
+                                         x2=actions)
         if self.variant in ("sac", "vsac"):
             return (self.local_critic_1(states, actions),
                     self.local_critic_2(states, actions))
@@ -411,11 +414,12 @@ class SACEngine:
 
     def _target_q(self, states, actions):
         if self._use_fused(states):
-            x = torch.cat([states, actions], dim=-1)
             if self._bf16:
+                x = torch.cat([states, actions], dim=-1)
                 return Fops.twin_mlp_forward_bf16(x, *self._twin_target,
                                                   self._target_chain.ws16)
-            return Fops.twin_mlp_forward(x, *self._twin_target)
+            return Fops.twin_mlp_forward(states, *self._twin_target,
+                                         x2=actions)
         if self.variant in ("sac", "vsac"):
             return (self.target_critic_1(states, actions),
                     self.target_critic_2(states, actions))
@@ -983,13 +987,15 @@ class SACEngine:
         self.refresh_bf16("critic")
 
         # --- actor/alpha step (post-critic-step critic, frozen heads) --
-        xa = torch.cat([states, sampled_actions], dim=-1)
         if self._bf16:
+            xa = torch.cat([states, sampled_actions], dim=-1)
             aq1, aq2 = Fops.twin_mlp_forward_bf16(xa,
                                                   *self._twin_local_frozen,
                                                   self._twin_local_bf16)
         else:
-            aq1, aq2 = Fops.twin_mlp_forward(xa, *self._twin_local_frozen)
+            aq1, aq2 = Fops.twin_mlp_forward(states,
+                                             *self._twin_local_frozen,
+                                             x2=sampled_actions)
         policy_loss, loss_log_alpha, entropy = Fops.actor_alpha_loss(
             aq1, aq2, log_probs, log_stds, states, self.log_alpha, T, use_w,
             self.H_bar_f)

@@ -11,6 +11,8 @@ instead of one per elementwise op — the backward chain is hand-written HIP.
 
 from __future__ import annotations
 
+import os
+from types import SimpleNamespace
 from typing import List, Optional, Sequence
 
 import torch
@@ -24,6 +26,59 @@ ACT_RELU = 1
 
 def _use_native(t: torch.Tensor) -> bool:
     return t.is_cuda and native_enabled()
+
+
+# ---------------------------------------------------------------------------
+# Whole-chain fp32 forward (k_f32_chain_fwd): opt-in with DSAC_F32_CHAIN=1.
+# Off (the default) not one launch changes.  On, an fp32 MLP forward whose
+# shapes the kernel serves is ONE launch instead of one per layer, and a
+# second input x2 is column-concatenated in the kernel's loader instead of
+# by a torch.cat launch.  Backward is the per-layer one either way.
+# ---------------------------------------------------------------------------
+
+def f32_chain_enabled() -> bool:
+    return os.environ.get("DSAC_F32_CHAIN", "0") == "1"
+
+
+def _f32_chain_ok(x1, x2, ws, bs, G: int) -> bool:
+    """The flag is on and mlp_chain_fwd_f32 accepts these arguments (its
+    own checks would raise otherwise): contiguous fp32 device tensors, at
+    most 6 layers, every width within the kernel's cap."""
+    if not f32_chain_enabled() or not 1 <= len(ws) <= 6:
+        return False
+    ts = [x1, *ws, *bs] + ([] if x2 is None else [x2])
+    if not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+               for t in ts):
+        return False
+    if x1.dim() != 2 or (x2 is not None and (
+            x2.dim() != 2 or x2.shape[0] != x1.shape[0])):
+        return False
+    if not all(w.dim() == 3 or (G == 1 and w.dim() == 2) for w in ws):
+        return False
+    cap = native().F32_CHAIN_MAX_WIDTH
+    k0 = x1.shape[1] + (0 if x2 is None else x2.shape[1])
+    return x1.shape[0] >= 1 and max(k0, *(w.shape[-2] for w in ws)) <= cap
+
+
+def _f32_chain_nograd(x1, x2, ws, bs, G: int):
+    """A forward nobody differentiates (target twin, frozen twin): no
+    activation is written to global memory."""
+    return native().mlp_chain_fwd_f32(x1, x2, list(ws), list(bs), G,
+                                      False)[0]
+
+
+def _cat_backward(base, ctx, *grads):
+    """Backward of a two-input ([x1 || x2]) chain forward: ``base``'s
+    backward on the single-input argument layout, its dx split by column."""
+    nig = ctx.needs_input_grad
+    shim = SimpleNamespace(
+        n_layers=ctx.n_layers, saved_tensors=ctx.saved_tensors,
+        grad_row_start=getattr(ctx, "grad_row_start", 0),
+        needs_input_grad=(nig[0] or nig[1],) + tuple(nig[2:]))
+    dx, *rest = base.backward(shim, *grads)
+    c1 = ctx.c1
+    return (dx[:, :c1] if nig[0] else None,
+            dx[:, c1:] if nig[1] else None, *rest)
 
 
 # ---------------------------------------------------------------------------
@@ -43,12 +98,17 @@ class _FusedMLP(torch.autograd.Function):
         ws = wb[:n_layers]
         bs = wb[n_layers:]
         ext = native()
-        acts: List[torch.Tensor] = [x]
-        h = x
-        for i in range(n_layers):
-            act = ACT_RELU if i < n_layers - 1 else ACT_NONE
-            h = ext.linear_act_fwd(h, ws[i], bs[i], act)
-            acts.append(h)
+        if _f32_chain_ok(x, None, ws, bs, 1):
+            h, saved = ext.mlp_chain_fwd_f32(x, None, list(ws), list(bs),
+                                             1, True)
+            acts: List[torch.Tensor] = [*saved, h]
+        else:
+            acts = [x]
+            h = x
+            for i in range(n_layers):
+                act = ACT_RELU if i < n_layers - 1 else ACT_NONE
+                h = ext.linear_act_fwd(h, ws[i], bs[i], act)
+                acts.append(h)
         ctx.save_for_backward(*acts, *ws)
         ctx.n_layers = n_layers
         ctx.grad_row_start = grad_row_start
@@ -85,18 +145,52 @@ class _FusedMLP(torch.autograd.Function):
         return (dx, None, None, *dws, *dbs)
 
 
+class _FusedMLPCat(torch.autograd.Function):
+    """_FusedMLP on x = [x1 || x2], concatenated by the chain kernel's
+    loader (which also saves the concatenation for backward)."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, n_layers: int, grad_row_start: int, *wb):
+        ws = wb[:n_layers]
+        bs = wb[n_layers:]
+        h, saved = native().mlp_chain_fwd_f32(x1, x2, list(ws), list(bs),
+                                              1, True)
+        ctx.save_for_backward(*saved, h, *ws)
+        ctx.n_layers = n_layers
+        ctx.grad_row_start = grad_row_start
+        ctx.c1 = x1.shape[1]
+        return h
+
+    @staticmethod
+    def backward(ctx, grad_out: torch.Tensor):
+        return _cat_backward(_FusedMLP, ctx, grad_out)
+
+
 def mlp_forward(x: torch.Tensor,
                 weights: Sequence[torch.Tensor],
                 biases: Sequence[torch.Tensor],
-                grad_row_start: int = 0) -> torch.Tensor:
+                grad_row_start: int = 0,
+                x2: Optional[torch.Tensor] = None) -> torch.Tensor:
     """ReLU-hidden MLP with linear output (reference build_mlp semantics).
 
     grad_row_start>0: rows [0, start) are forward-only (their output grads
     are structurally zero — e.g. the TD half of a batched actor pass), so
-    backward runs on the remaining rows only."""
+    backward runs on the remaining rows only.
+
+    x2: the MLP's input is [x || x2] (columns)."""
     if _use_native(x):
+        if _f32_chain_ok(x, x2, weights, biases, 1):
+            if not torch.is_grad_enabled():
+                return _f32_chain_nograd(x, x2, weights, biases, 1)
+            if x2 is not None:
+                return _FusedMLPCat.apply(x, x2, len(weights),
+                                          grad_row_start, *weights, *biases)
+        elif x2 is not None:
+            x = torch.cat([x, x2], dim=-1)
         return _FusedMLP.apply(x, len(weights), grad_row_start,
                                *weights, *biases)
+    if x2 is not None:
+        x = torch.cat([x, x2], dim=-1)
     return torch_ref.mlp_forward(x, weights, biases)
 
 
@@ -157,12 +251,17 @@ class _FusedTwinMLP(torch.autograd.Function):
         ws = wb[:n_layers]      # each [2, N, K]
         bs = wb[n_layers:]      # each [2, N]
         ext = native()
-        acts = [x]
-        h = x
-        for i in range(n_layers):
-            act = ACT_RELU if i < n_layers - 1 else ACT_NONE
-            h = ext.linear_act_fwd_g(h, ws[i], bs[i], act, 2)
-            acts.append(h)
+        if _f32_chain_ok(x, None, ws, bs, 2):
+            h, saved = ext.mlp_chain_fwd_f32(x, None, list(ws), list(bs),
+                                             2, True)
+            acts = [*saved, h]
+        else:
+            acts = [x]
+            h = x
+            for i in range(n_layers):
+                act = ACT_RELU if i < n_layers - 1 else ACT_NONE
+                h = ext.linear_act_fwd_g(h, ws[i], bs[i], act, 2)
+                acts.append(h)
         ctx.save_for_backward(*acts, *ws)
         ctx.n_layers = n_layers
         return h[0], h[1]
@@ -192,9 +291,40 @@ class _FusedTwinMLP(torch.autograd.Function):
         return (dx, None, *dws, *dbs)
 
 
-def twin_mlp_forward(x: torch.Tensor, stacked_ws, stacked_bs):
+class _FusedTwinMLPCat(torch.autograd.Function):
+    """_FusedTwinMLP on x = [x1 || x2] ([states || actions]), concatenated
+    by the chain kernel's loader."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, n_layers: int, *wb):
+        ws = wb[:n_layers]
+        bs = wb[n_layers:]
+        h, saved = native().mlp_chain_fwd_f32(x1, x2, list(ws), list(bs),
+                                              2, True)
+        ctx.save_for_backward(*saved, h, *ws)
+        ctx.n_layers = n_layers
+        ctx.c1 = x1.shape[1]
+        return h[0], h[1]
+
+    @staticmethod
+    def backward(ctx, dq1: torch.Tensor, dq2: torch.Tensor):
+        return _cat_backward(_FusedTwinMLP, ctx, dq1, dq2)
+
+
+def twin_mlp_forward(x: torch.Tensor, stacked_ws, stacked_bs,
+                     x2: Optional[torch.Tensor] = None):
     """Both Q heads in one grouped launch per layer.  stacked_ws[i] is a
-    [2,N,K] view into the critic flat parameter buffer."""
+    [2,N,K] view into the critic flat parameter buffer.  x2: the input is
+    [x || x2] (columns)."""
+    if _f32_chain_ok(x, x2, stacked_ws, stacked_bs, 2):
+        if not torch.is_grad_enabled():
+            h = _f32_chain_nograd(x, x2, stacked_ws, stacked_bs, 2)
+            return h[0], h[1]
+        if x2 is not None:
+            return _FusedTwinMLPCat.apply(x, x2, len(stacked_ws),
+                                          *stacked_ws, *stacked_bs)
+    elif x2 is not None:
+        x = torch.cat([x, x2], dim=-1)
     return _FusedTwinMLP.apply(x, len(stacked_ws), *stacked_ws, *stacked_bs)
 
 

@@ -25,7 +25,8 @@ setup(
             sources=["distributed_sac_amd/ops/_hip/dsac_kernels.hip",
                      "distributed_sac_amd/ops/_hip/shm_ring.cpp",
                      "distributed_sac_amd/ops/_hip/bf16_gemm.hip",
-                     "distributed_sac_amd/ops/_hip/chain_gemm.hip"],
+                     "distributed_sac_amd/ops/_hip/chain_gemm.hip",
+                     "distributed_sac_amd/ops/_hip/f32_chain.hip"],
             extra_compile_args={
                 "cxx": ["-O3"],
                 "nvcc": ["-O3", "--offload-arch=gfx950"],
