@@ -33,7 +33,8 @@ def _use_native(t: torch.Tensor) -> bool:
 # Off (the default) not one launch changes.  On, an fp32 MLP forward whose
 # shapes the kernel serves is ONE launch instead of one per layer, and a
 # second input x2 is column-concatenated in the kernel's loader instead of
-# by a torch.cat launch.  Backward is the per-layer one either way.
+# by a torch.cat launch.  Backward is the per-layer one unless
+# DSAC_F32_CHAIN_BWD=1 (below).
 # ---------------------------------------------------------------------------
 
 def f32_chain_enabled() -> bool:
@@ -67,6 +68,73 @@ def _f32_chain_nograd(x1, x2, ws, bs, G: int):
                                       False)[0]
 
 
+# ---------------------------------------------------------------------------
+# Whole-chain fp32 backward (k_f32_chain_dx, k_f32_chain_dwdb): opt-in with
+# DSAC_F32_CHAIN_BWD=1, independent of DSAC_F32_CHAIN (both forward paths
+# save the same tensors).  Off (the default) not one launch changes.  On,
+# the backward of an fp32 MLP of two or more layers is three launches — the
+# dx walk, the grouped split-K dW/db, one arena fold — instead of up to
+# five per layer.
+# ---------------------------------------------------------------------------
+
+def f32_chain_bwd_enabled() -> bool:
+    return os.environ.get("DSAC_F32_CHAIN_BWD", "0") == "1"
+
+
+def _f32_chain_bwd_ok(dy, acts, ws, G: int) -> bool:
+    """The flag is on and the chain-backward bindings accept these
+    arguments: contiguous fp32 device tensors, 2 to 6 layers (a single
+    layer stays per-layer), every width within the kernel's cap."""
+    if not f32_chain_bwd_enabled() or not 2 <= len(ws) <= 6:
+        return False
+    if not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+               for t in (dy, *acts, *ws)):
+        return False
+    if not all(w.dim() == 3 or (G == 1 and w.dim() == 2) for w in ws):
+        return False
+    cap = native().F32_CHAIN_MAX_WIDTH
+    return dy.shape[-2] >= 1 and max(
+        ws[0].shape[-1], *(w.shape[-2] for w in ws)) <= cap
+
+
+def _f32_chain_bwd_slices(ws, G: int, M: int) -> int:
+    """Split-K slices of the grouped dW/db launch.  Its workgroups are one
+    wave each, so aim at about two waves per SIMD (8 workgroups per CU);
+    a slice is at least 4 batch rows."""
+    jobs = G * sum(-(-w.shape[-2] // 64) * -(-w.shape[-1] // 64) for w in ws)
+    cus = torch.cuda.get_device_properties(ws[0].device).multi_processor_count
+    return max(1, min(-(-8 * cus // jobs), -(-M // 4)))
+
+
+def _f32_chain_bwd(dy, acts, ws, G: int, dx0_lo: int, need_w):
+    """``(dx0, dws, dbs)`` of a whole chain.  ``acts[l]`` is the input of
+    layer l; ``dx0_lo < 0``: no input gradient, else its columns from
+    ``dx0_lo`` on.  ``dws[l]`` / ``dbs[l]`` are views of one flat tensor
+    (the dW/db arena's layout: every dW in layer order, then every db) for
+    the layers ``need_w`` marks, None for the others."""
+    ext = native()
+    n = len(ws)
+    dys, dx0 = ext.mlp_chain_bwd_dx_f32(dy, list(ws), list(acts), G, dx0_lo)
+    dws: List[Optional[torch.Tensor]] = [None] * n
+    dbs: List[Optional[torch.Tensor]] = [None] * n
+    if any(need_w):
+        S = _f32_chain_bwd_slices(ws, G, dy.shape[-2])
+        arena = ext.mlp_chain_bwd_dwdb_f32([*dys, dy], list(acts), G, S)
+        flat = torch.empty(arena.shape[1], dtype=dy.dtype, device=dy.device)
+        ext.reduce_arena(arena, flat, S)
+        off = 0
+        for i, w in enumerate(ws):
+            if need_w[i]:
+                dws[i] = flat[off:off + w.numel()].view(w.shape)
+            off += w.numel()
+        for i, w in enumerate(ws):
+            nb = w.numel() // w.shape[-1]
+            if need_w[i]:
+                dbs[i] = flat[off:off + nb].view(w.shape[:-1])
+            off += nb
+    return dx0, dws, dbs
+
+
 def _cat_backward(base, ctx, *grads):
     """Backward of a two-input ([x1 || x2]) chain forward: ``base``'s
     backward on the single-input argument layout, its dx split by column."""
@@ -74,9 +142,13 @@ def _cat_backward(base, ctx, *grads):
     shim = SimpleNamespace(
         n_layers=ctx.n_layers, saved_tensors=ctx.saved_tensors,
         grad_row_start=getattr(ctx, "grad_row_start", 0),
+        dx0_lo=0 if nig[0] else ctx.c1,
         needs_input_grad=(nig[0] or nig[1],) + tuple(nig[2:]))
     dx, *rest = base.backward(shim, *grads)
     c1 = ctx.c1
+    if dx is not None and not nig[0]:
+        # the chain backward skipped x1's columns, the per-layer one did not
+        c1 -= ctx.saved_tensors[ctx.n_layers + 1].shape[-1] - dx.shape[1]
     return (dx[:, :c1] if nig[0] else None,
             dx[:, c1:] if nig[1] else None, *rest)
 
@@ -129,6 +201,12 @@ class _FusedMLP(torch.autograd.Function):
             acts = [a[r0:] for a in acts]
             grad_out = grad_out[r0:]
         dy = grad_out.contiguous()
+        if _f32_chain_bwd_ok(dy, acts[:n], ws, 1):
+            dx, dws, dbs = _f32_chain_bwd(
+                dy, acts[:n], ws, 1,
+                getattr(ctx, "dx0_lo", 0) if ctx.needs_input_grad[0] else -1,
+                ctx.needs_input_grad[3:3 + n])
+            return (dx, None, None, *dws, *dbs)
         dws: List[Optional[torch.Tensor]] = [None] * n
         dbs: List[Optional[torch.Tensor]] = [None] * n
         for i in range(n - 1, -1, -1):
@@ -274,6 +352,12 @@ class _FusedTwinMLP(torch.autograd.Function):
         ws = saved[n + 1:]
         ext = native()
         dy = torch.stack([dq1, dq2], dim=0).contiguous()  # [2,B,Nout]
+        if _f32_chain_bwd_ok(dy, acts[:n], ws, 2):
+            dx, dws, dbs = _f32_chain_bwd(
+                dy, acts[:n], ws, 2,
+                getattr(ctx, "dx0_lo", 0) if ctx.needs_input_grad[0] else -1,
+                ctx.needs_input_grad[2:2 + n])
+            return (dx, None, *dws, *dbs)
         dws = [None] * n
         dbs = [None] * n
         for i in range(n - 1, -1, -1):

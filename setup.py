@@ -26,7 +26,8 @@ setup(
                      "distributed_sac_amd/ops/_hip/shm_ring.cpp",
                      "distributed_sac_amd/ops/_hip/bf16_gemm.hip",
                      "distributed_sac_amd/ops/_hip/chain_gemm.hip",
-                     "distributed_sac_amd/ops/_hip/f32_chain.hip"],
+                     "distributed_sac_amd/ops/_hip/f32_chain.hip",
+                     "distributed_sac_amd/ops/_hip/f32_chain_bwd.hip"],
             extra_compile_args={
                 "cxx": ["-O3"],
                 "nvcc": ["-O3", "--offload-arch=gfx950"],
