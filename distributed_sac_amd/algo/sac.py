@@ -32,6 +32,7 @@ import torch.nn as nn
 from ..config import SACConfig
 from ..models import Actor, Critic, LLActor, LLCritic
 from ..ops import functional as Fops
+from ..ops import torch_ref
 from ..ops.chain import ManualChain, forward_pair, pack_chains
 from ..ops.flat import FlatParams, FusedAdam, flat_polyak_
 
@@ -80,6 +81,10 @@ class SACEngine:
         self._graph_chunk = 1
         self._dp_graphs = None
         self.context_encoder_optimizer = None
+        # truncated quantile critics: M atoms per Q network (0 = scalar
+        # critics), tqc_drop atoms per network cut from the pooled target
+        self.tqc_M, self.tqc_drop = cfg.critic_quantiles_choice
+        self._tqc_unsupported()
         self._build_models()
         self._build_optimizers()
         self._init_grad_clip(max_grad_norm)
@@ -146,17 +151,15 @@ class SACEngine:
     # ------------------------------------------------------------------
     def _build_models(self) -> None:
         cfg, dev = self.cfg, self.device
+        head = max(1, self.tqc_M)
         if self.variant in ("sac", "vsac"):
             self.actor = LLActor(cfg.state_dim, cfg.action_dim,
                                  cfg.actor_hidden_dim, cfg.action_bound).to(dev)
-            self.local_critic_1 = LLCritic(cfg.state_dim, cfg.action_dim,
-                                           cfg.critic_hidden_dim).to(dev)
-            self.local_critic_2 = LLCritic(cfg.state_dim, cfg.action_dim,
-                                           cfg.critic_hidden_dim).to(dev)
-            self.target_critic_1 = LLCritic(cfg.state_dim, cfg.action_dim,
-                                            cfg.critic_hidden_dim).to(dev)
-            self.target_critic_2 = LLCritic(cfg.state_dim, cfg.action_dim,
-                                            cfg.critic_hidden_dim).to(dev)
+            self.local_critic_1, self.local_critic_2, \
+                self.target_critic_1, self.target_critic_2 = (
+                    LLCritic(cfg.state_dim, cfg.action_dim,
+                             cfg.critic_hidden_dim, head_width=head).to(dev)
+                    for _ in range(4))
             self.log_alpha = nn.Parameter(torch.tensor(
                 [float(cfg.log_alpha)], device=dev))
         elif self.variant == "mtsac":
@@ -165,10 +168,12 @@ class SACEngine:
                                num_tasks=cfg.num_tasks).to(dev)
             self.local_critic = Critic(cfg.state_dim, cfg.action_dim,
                                        cfg.critic_hidden_dim,
-                                       num_tasks=cfg.num_tasks).to(dev)
+                                       num_tasks=cfg.num_tasks,
+                                       head_width=head).to(dev)
             self.target_critic = Critic(cfg.state_dim, cfg.action_dim,
                                         cfg.critic_hidden_dim,
-                                        num_tasks=cfg.num_tasks).to(dev)
+                                        num_tasks=cfg.num_tasks,
+                                        head_width=head).to(dev)
             # per-task log_alpha (reference MT10…MTSAC/src/learner.py:115-121)
             self.log_alpha = nn.Parameter(torch.full(
                 (cfg.num_tasks,), float(cfg.log_alpha), device=dev))
@@ -293,6 +298,9 @@ class SACEngine:
         # the fused actor/alpha fwd+bwd kernel: one ticket, 32x4 metric
         # slots, then up to 32 blocks x 32 tasks of alpha-gradient slots
         self._aafb_ws = torch.zeros(1 + 32 * 4 + 32 * 32, device=dev)
+        if self.tqc_M:
+            # the quantile critic loss: one ticket, 1024 blocks x 2 slots
+            self._tqc_ws = torch.zeros(1 + 2 * 1024, device=dev)
         # persistent counter for the in-kernel RNG, seeded from the torch
         # seed so runs stay reproducible end-to-end
         self._rng_ctr = torch.tensor(
@@ -451,6 +459,40 @@ class SACEngine:
         if why is not None:
             raise NotImplementedError(f"prioritized replay: {why}")
 
+    # -- truncated quantile critics ----------------------------------------
+    def _tqc_unsupported(self) -> None:
+        """Raise for the combinations truncated quantile critics do not
+        cover (checked at construction and again per update, where the
+        batch and the environment switches are known)."""
+        if not self.tqc_M:
+            return
+        from ..ops import has_native, native_enabled
+        why = None
+        if self.variant == "care":
+            why = "CAREEngine has no quantile-critic path"
+        elif self._per is not None:
+            why = "not supported together with prioritized replay"
+        elif self.degenerate_w and self.use_weighted_loss:
+            why = "not defined for weighted_loss_mode='reference'"
+        elif self.device.type == "cuda" and native_enabled() \
+                and has_native() and not (
+                self.precision == "bf16"
+                and os.environ.get("DSAC_NO_MANUAL", "0") != "1"):
+            why = ("on a GPU only the bf16 manual-backward path has the "
+                   "quantile loss kernels (not the fp32 path, not "
+                   "DSAC_NO_MANUAL=1)")
+        if why is not None:
+            raise NotImplementedError(f"truncated quantile critics: {why}")
+
+    def _row_coeff(self, states: torch.Tensor) -> torch.Tensor:
+        """The loss coefficient of every row, ``[B]``: 1/B, or the
+        normalized task weight / B under ``use_weighted_loss``."""
+        B = states.shape[0]
+        if self.use_weighted_loss:
+            return Fops.task_weights(states[:, -self.num_tasks:],
+                                     self.log_alpha.exp().detach()) / B
+        return states.new_full((B,), 1.0 / B)
+
     def attach_per(self, replay) -> None:
         """Pair with a ``sampling="prioritized"`` replay: its per_alpha /
         per_eps shape the new priorities, and every update of a batch that
@@ -458,6 +500,7 @@ class SACEngine:
         ``replay.update_priorities`` (inside the graph when captured)."""
         self._per_unsupported()
         self._per = replay
+        self._tqc_unsupported()
 
     def _per_params(self):
         src = self._per if self._per is not None else self.cfg
@@ -509,6 +552,12 @@ class SACEngine:
         per = "is_weights" in batch
         if per:
             self._per_unsupported()
+        if self.tqc_M:
+            if per:
+                raise NotImplementedError(
+                    "truncated quantile critics: not supported together "
+                    "with prioritized replay")
+            self._tqc_unsupported()
         out = self._update_tensors(batch)
         if per and self._per is not None:
             self.per_write_back(self._per)
@@ -535,12 +584,21 @@ class SACEngine:
         with torch.no_grad():
             next_actions, next_log_probs, _ = self._sample(next_states)
             q1_t, q2_t = self._target_q(next_states, next_actions)
-            y = Fops.td_target(rewards, dones, q1_t, q2_t, next_log_probs,
-                               alpha, self.gamma, self.reward_scale)
+            if self.tqc_M:
+                y = torch_ref.tqc_target(
+                    rewards, dones, q1_t, q2_t, next_log_probs, alpha,
+                    self.gamma, self.reward_scale, self.tqc_drop)
+            else:
+                y = Fops.td_target(rewards, dones, q1_t, q2_t,
+                                   next_log_probs, alpha, self.gamma,
+                                   self.reward_scale)
 
         # --- critic step ---------------------------------------------
-        if "is_weights" in batch:
-            from ..ops import torch_ref
+        if self.tqc_M:
+            l1, l2 = torch_ref.tqc_critic_loss(
+                *self._critic_q(states, actions), y, self._row_coeff(states))
+            q_loss = l1 + l2
+        elif "is_weights" in batch:
             w = batch["is_weights"].reshape(-1, 1)
             q_loss, d1, d2 = self._critic_loss_per(states, actions, y,
                                                    w / w.max())
@@ -566,7 +624,7 @@ class SACEngine:
         # --- actor step ----------------------------------------------
         sampled_actions, log_probs, log_stds = self._sample(states)
         q1, q2 = self._critic_q(states, sampled_actions)
-        q_min = torch.min(q1, q2)
+        q_min = torch_ref.tqc_q(q1, q2) if self.tqc_M else torch.min(q1, q2)
         if self.variant == "mtsac":
             policy_loss = self.actor.cal_loss(
                 log_probs, q_min, alpha,
@@ -783,6 +841,13 @@ class SACEngine:
         T = self.num_tasks
         use_w = self.use_weighted_loss
         la_det = self.log_alpha.detach()
+        if self.tqc_M:
+            # the four heads are [B, M] atoms: pooled, sorted, truncated
+            # target + quantile Huber loss + d theta in one launch
+            return ext.tqc_critic_loss(
+                rewards, dones, q1_t, q2_t, nlp, q1, q2, states, la_det, T,
+                int(use_w), self.gamma, self.reward_scale, self.tqc_drop,
+                self._tqc_ws)
         # one launch for TD target + loss fwd + dq (its grid covers the
         # batch in <= 32 blocks); a larger batch keeps the three launches
         fuse_loss = self._fuse_tail and states.shape[0] <= 8192
@@ -852,7 +917,13 @@ class SACEngine:
         fuse = self._fuse_tail
         # the fwd kernel zeroes the alpha flat grad in passing (the bwd's
         # atomics target) — no separate fill launch
-        if fuse and B <= 8192:
+        if self.tqc_M:
+            # Q = the mean of the 2M atoms; daq [2, B, M]
+            al, daq, dlp = ext.tqc_actor_alpha_loss_fwd_bwd(
+                aq1, aq2, lp, ls, states, la_det,
+                self.alpha_group.flat_grad, T, int(use_w), self.H_bar_f,
+                self._aafb_ws, st["closs"][2:3] if use_w else None)
+        elif fuse and B <= 8192:
             # forward metrics, dq/dlp and the alpha flat grad in one launch.
             # The weighted-loss normalizer is the one the critic loss of
             # this update finalized (closs[2]: same states, same log_alpha
@@ -1160,6 +1231,16 @@ class SACEngine:
         self.update_iteration = int(ckpt.get("update_iteration",
                                              ckpt.get("episode_idx", 0)))
         self.total_step = int(ckpt.get("total_step", 0))
+        # the keys of a scalar and a quantile critic are the same; only the
+        # last layer's shape tells them apart
+        sd = ckpt["local_critic_1" if self.variant in ("sac", "vsac")
+                  else "local_critic"]
+        saved = [v for k, v in sd.items() if k.endswith("weight")][-1].shape[0]
+        if saved != max(1, self.tqc_M):
+            raise ValueError(
+                f"checkpoint critics have head width {saved}, this engine "
+                f"has {max(1, self.tqc_M)} (critic_quantiles = "
+                f"{self.tqc_M}; 1 = scalar critics)")
         self.actor.load_state_dict(ckpt["actor"])
         if self.variant in ("sac", "vsac"):
             self.local_critic_1.load_state_dict(ckpt["local_critic_1"])

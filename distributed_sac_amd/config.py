@@ -113,6 +113,13 @@ class SACConfig:
     # finite.  None (a cfg without the key) = off; inf = guard and metrics
     # only.  See docs/KERNELS.md "Gradient-norm clipping".
     max_grad_norm: Optional[float] = None
+    # net-new (the reference has none): truncated quantile critics.  Each Q
+    # network predicts critic_quantiles atoms (None, a cfg without the key:
+    # DSAC_CRITIC_QUANTILES, else 0 = scalar critics); the TD target drops
+    # the critic_quantiles_drop largest atoms per network of the pooled
+    # target.  See docs/KERNELS.md "Truncated quantile critics".
+    critic_quantiles: Optional[int] = None
+    critic_quantiles_drop: Optional[int] = None
     # CARE-only block (reference cfg "encoder"):
     encoder: Optional[Dict[str, Any]] = None
     use_modified_care: bool = False
@@ -154,6 +161,26 @@ class SACConfig:
             raise ValueError(
                 f"DSAC_MAX_GRAD_NORM must be a positive number, got {env!r}")
         return check_max_grad_norm(v)
+
+    @property
+    def critic_quantiles_choice(self):
+        """``(M, drop)``: the cfg's ``critic_quantiles`` /
+        ``critic_quantiles_drop`` where set, else ``DSAC_CRITIC_QUANTILES``
+        / ``DSAC_CRITIC_QUANTILES_DROP``, else 0 (scalar critics) / 2."""
+        from .ops.torch_ref import check_critic_quantiles
+        vals = []
+        for v, env, default in (
+                (self.critic_quantiles, "DSAC_CRITIC_QUANTILES", 0),
+                (self.critic_quantiles_drop, "DSAC_CRITIC_QUANTILES_DROP",
+                 2)):
+            if v is None:
+                s = os.environ.get(env, "")
+                try:
+                    v = int(s) if s != "" else default
+                except ValueError:
+                    raise ValueError(f"{env} must be an integer, got {s!r}")
+            vals.append(v)
+        return check_critic_quantiles(*vals)
 
     @property
     def per_kwargs(self) -> Dict[str, Any]:
@@ -226,6 +253,14 @@ class SACConfig:
             if c.max_grad_norm is None:
                 raise ValueError("max_grad_norm must be a positive number, "
                                  "got None (leave the key out for off)")
+        for key in ("critic_quantiles", "critic_quantiles_drop"):
+            if key in cfg:
+                setattr(c, key, cfg[key])
+        if c.critic_quantiles is not None:
+            from .ops.torch_ref import check_critic_quantiles
+            check_critic_quantiles(
+                c.critic_quantiles, 2 if c.critic_quantiles_drop is None
+                else c.critic_quantiles_drop)
         if "use_modified_care" in cfg:
             c.use_modified_care = bool(cfg["use_modified_care"])
         if "encoder" in cfg:

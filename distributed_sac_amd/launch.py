@@ -53,6 +53,16 @@ def main():
                          "global L2 norm and skip non-finite steps (inf: "
                          "guard only; default: the cfg's max_grad_norm, "
                          "else DSAC_MAX_GRAD_NORM, else off)")
+    ap.add_argument("--critic-quantiles", type=int, default=None,
+                    help="truncated quantile critics: atoms per Q network, "
+                         "0 = scalar critics (default: the cfg's "
+                         "critic_quantiles, else DSAC_CRITIC_QUANTILES, "
+                         "else 0)")
+    ap.add_argument("--critic-quantiles-drop", type=int, default=None,
+                    help="atoms per network dropped from the top of the "
+                         "pooled target (default: the cfg's "
+                         "critic_quantiles_drop, else "
+                         "DSAC_CRITIC_QUANTILES_DROP, else 2)")
     # eval mode
     ap.add_argument("--eval", action="store_true")
     ap.add_argument("--checkpoint", default=None)
@@ -71,6 +81,12 @@ def main():
         cfg = SACConfig.from_file(args.cfg, variant)
     else:
         cfg = load_variant(args.variant)
+    # an argument overrides the cfg's key (which overrides the environment)
+    if args.critic_quantiles is not None:
+        cfg.critic_quantiles = args.critic_quantiles
+    if args.critic_quantiles_drop is not None:
+        cfg.critic_quantiles_drop = args.critic_quantiles_drop
+    cfg.critic_quantiles_choice   # validate before anything starts
 
     env_fn = default_env_fn
     if args.env:

@@ -22,15 +22,17 @@ class Critic(nn.Module):
     """Twin Q on [mtobs || action]; keys ``Q_function_{1,2}.{0,2,4,6}.*``."""
 
     def __init__(self, state_dim: int, action_dim: int,
-                 hidden_dims: List[int], num_tasks: int = 0):
+                 hidden_dims: List[int], num_tasks: int = 0,
+                 head_width: int = 1):
         super().__init__()
         self.state_dim = state_dim
         self.num_tasks = num_tasks
+        self.head_width = head_width   # 1: scalar Q; M: quantile atoms
         self.mtobs_dim = state_dim + num_tasks
         self.action_dim = action_dim
         in_dim = self.mtobs_dim + action_dim
-        self.Q_function_1 = build_mlp(in_dim, 1, hidden_dims)
-        self.Q_function_2 = build_mlp(in_dim, 1, hidden_dims)
+        self.Q_function_1 = build_mlp(in_dim, head_width, hidden_dims)
+        self.Q_function_2 = build_mlp(in_dim, head_width, hidden_dims)
         self.Q_function_1.apply(weights_init)
         self.Q_function_2.apply(weights_init)
 
@@ -69,11 +71,12 @@ class LLCritic(nn.Module):
     ``layer_module.{0,1}.*`` (LunarLander…/src/model.py:92-142)."""
 
     def __init__(self, state_dim: int, action_dim: int,
-                 hidden_dim: List[int] = (256, 256)):
+                 hidden_dim: List[int] = (256, 256), head_width: int = 1):
         super().__init__()
         self.state_dim = state_dim
         self.action_dim = action_dim
-        dims = list(hidden_dim) + [1]
+        self.head_width = head_width   # 1: scalar Q; M: quantile atoms
+        dims = list(hidden_dim) + [head_width]
         self.first_layer = nn.Linear(state_dim + action_dim, hidden_dim[0])
         self.layer_module = nn.ModuleList(
             [nn.Linear(i, o) for i, o in zip(dims[:-1], dims[1:])])

@@ -86,6 +86,68 @@ def td_target(rewards: torch.Tensor, dones: torch.Tensor,
         torch.min(q1_target, q2_target) - alpha * next_log_probs)
 
 
+# ---------------------------------------------------------------------------
+# Truncated quantile critics (Kuznetsov et al., 2020; net-new, the reference
+# has none).  Each Q network predicts M atoms; the functions work in the
+# dtype of their inputs, so float64 inputs make them the kernels' oracle
+# (docs/KERNELS.md "Truncated quantile critics").
+# ---------------------------------------------------------------------------
+
+def check_critic_quantiles(M, drop=2):
+    """``(M, drop)`` as ints: M atoms per network (0 = scalar critics) and
+    atoms dropped per network.  Raises ValueError outside ``0 <= M <= 32``
+    (one wave64 holds a row's 2M atoms) or ``0 <= drop < M``."""
+    for name, v in (("critic_quantiles", M), ("critic_quantiles_drop", drop)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+    if not 0 <= M <= 32:
+        raise ValueError(
+            f"critic_quantiles must be in 0..32 (0 = off), got {M}")
+    if M and not 0 <= drop < M:
+        raise ValueError(
+            f"critic_quantiles_drop must be in 0..{M - 1} "
+            f"(critic_quantiles = {M}), got {drop}")
+    return M, drop
+
+
+def tqc_target(rewards, dones, z1_target, z2_target, next_log_probs, alpha,
+               gamma: float, reward_scale: float, drop: int) -> torch.Tensor:
+    """``y [B, K]``, K = 2M - 2*drop: the pooled target atoms ``[B, M]`` of
+    both networks sorted ascending, the K smallest mapped through the
+    Bellman backup.  The raw atoms are sorted (the map is monotone); a row
+    with a NaN atom is NaN throughout."""
+    z = torch.cat([z1_target, z2_target], dim=1)
+    K = z.shape[1] - 2 * drop
+    zs = torch.sort(z, dim=1).values[:, :K]
+    y = reward_scale * rewards + gamma * (1 - dones) * (
+        zs - alpha * next_log_probs)
+    bad = torch.isnan(z).any(dim=1, keepdim=True)
+    return torch.where(bad, torch.full_like(y, float("nan")), y)
+
+
+def tqc_critic_loss(theta1, theta2, y, coeff):
+    """Quantile Huber losses ``(L_1, L_2)`` of the atoms ``theta_n [B, M]``
+    against ``y [B, K]``: tau_i = (2i+1)/(2M), u = y_k - theta_i,
+    rho = |tau_i - 1{u<0}| * H(u) with the Huber H at 1, averaged over the
+    M*K pairs and summed over rows with the row coefficients ``coeff [B]``
+    (1/B, or the normalized task weight / B)."""
+    M = theta1.shape[1]
+    tau = (2 * torch.arange(M, dtype=y.dtype, device=y.device) + 1) / (2 * M)
+    out = []
+    for th in (theta1, theta2):
+        u = y.unsqueeze(1) - th.unsqueeze(2)           # [B, M, K]
+        au = u.abs()
+        h = torch.where(au <= 1, 0.5 * u * u, au - 0.5)
+        rho = (tau.view(1, M, 1) - (u < 0).to(y.dtype)).abs() * h
+        out.append((coeff.reshape(-1) * rho.mean(dim=(1, 2))).sum())
+    return out[0], out[1]
+
+
+def tqc_q(z1, z2) -> torch.Tensor:
+    """Q(s, a) ``[B, 1]`` of a quantile twin: the mean of its 2M atoms."""
+    return torch.cat([z1, z2], dim=1).mean(dim=1, keepdim=True)
+
+
 def task_weights(one_hots: torch.Tensor, alphas: torch.Tensor) -> torch.Tensor:
     """Per-sample weights for the weighted multi-task loss.
 

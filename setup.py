@@ -27,7 +27,8 @@ setup(
                      "distributed_sac_amd/ops/_hip/bf16_gemm.hip",
                      "distributed_sac_amd/ops/_hip/chain_gemm.hip",
                      "distributed_sac_amd/ops/_hip/f32_chain.hip",
-                     "distributed_sac_amd/ops/_hip/f32_chain_bwd.hip"],
+                     "distributed_sac_amd/ops/_hip/f32_chain_bwd.hip",
+                     "distributed_sac_amd/ops/_hip/tqc.hip"],
             extra_compile_args={
                 "cxx": ["-O3"],
                 "nvcc": ["-O3", "--offload-arch=gfx950"],
