@@ -85,6 +85,14 @@ class SACEngine:
         # critics), tqc_drop atoms per network cut from the pooled target
         self.tqc_M, self.tqc_drop = cfg.critic_quantiles_choice
         self._tqc_unsupported()
+        # PCGrad gradient surgery between the per-task gradients of the
+        # critic and of the actor group (docs/KERNELS.md "PCGrad")
+        self.pcgrad = cfg.pcgrad_choice
+        self._pcgrad_seed = int(torch.initial_seed()) & 0x7FFFFFFF
+        self._pcgrad_updates = 0
+        self._pcgrad_out: dict = {}
+        self._pcgrad_ws: Optional[torch.Tensor] = None
+        self._pcgrad_unsupported()
         self._build_models()
         self._build_optimizers()
         self._init_grad_clip(max_grad_norm)
@@ -372,6 +380,7 @@ class SACEngine:
         """Join a data-parallel group: sync replicas, then every update
         all-reduces the flat gradient buffers (one RCCL message each)."""
         self.ddp = ddp
+        self._pcgrad_unsupported()
         if ddp is not None and ddp.enabled:
             ddp.broadcast_params(self.actor_group.flat_data)
             ddp.broadcast_params(self.critic_group.flat_data)
@@ -484,6 +493,99 @@ class SACEngine:
         if why is not None:
             raise NotImplementedError(f"truncated quantile critics: {why}")
 
+    # -- PCGrad ------------------------------------------------------------
+    def _pcgrad_unsupported(self, B: Optional[int] = None) -> None:
+        """Raise for the combinations PCGrad does not cover (checked at
+        construction and again per update, where the batch, the attached
+        group and the environment switches are known)."""
+        if not self.pcgrad:
+            return
+        from ..ops import has_native, native_enabled
+        T = self.num_tasks
+        gpu = self.device.type == "cuda" and native_enabled() \
+            and has_native()
+        why = None
+        if self.variant == "care":
+            why = "CAREEngine has no per-task gradient arena"
+        elif not 2 <= T <= torch_ref.PCGRAD_MAX_T:
+            why = (f"num_tasks must be in 2..{torch_ref.PCGRAD_MAX_T} "
+                   f"(variant mtsac), got {T}")
+        elif self.ddp is not None and getattr(self.ddp, "enabled", True):
+            why = ("not supported with a data-parallel group attached (the "
+                   "[T, numel] arena would need the all-reduce)")
+        elif self.degenerate_w and self.use_weighted_loss:
+            why = "not defined for weighted_loss_mode='reference'"
+        elif gpu and self.precision != "bf16":
+            why = ("on a GPU only the bf16 manual-backward path writes "
+                   "per-task gradients (not the fp32 GPU path)")
+        elif gpu and os.environ.get("DSAC_NO_MANUAL", "0") == "1":
+            why = "the autograd bf16 path (DSAC_NO_MANUAL=1) has no arena"
+        elif gpu and os.environ.get("DSAC_KRNG", "1") != "1":
+            why = ("the visiting orders come from the device counter RNG "
+                   "(DSAC_KRNG=0 turns it off)")
+        elif B is not None and B % T:
+            why = (f"the batch ({B} rows) must divide into num_tasks = {T} "
+                   "equal parts (B % T != 0)")
+        if why is not None:
+            raise NotImplementedError(f"pcgrad: {why}")
+
+    def _pcgrad_cpu(self, name: str, rows: torch.Tensor, states, group):
+        """The torch path of one group: ``rows [B]`` are the per-row terms
+        whose sum is the group's loss.  Forms the T per-task gradients with
+        autograd on the per-task partial sums, runs the oracle and writes
+        the surgered gradient to ``group.flat_grad``.  Returns the share of
+        visited pairs that were projected."""
+        T = self.num_tasks
+        per = torch_ref.pcgrad_task_rows(states[:, -T:], T)
+        arena = rows.new_zeros(T, group.numel)
+        for t, part in enumerate(rows.reshape(T, per).sum(dim=1)):
+            gs = torch.autograd.grad(part, group.params, retain_graph=True,
+                                     allow_unused=True)
+            for g, p, off in zip(gs, group.params, group.offsets):
+                if g is not None:
+                    arena[t, off:off + p.numel()] = g.reshape(-1)
+        # the critic at the update's counter, the actor one past it: on the
+        # GPU the Adam prolog bumps the device counter between the two
+        ctr = self._pcgrad_seed + self._pcgrad_updates \
+            + torch_ref.PCGRAD_GROUPS[name]
+        w, _, projected = torch_ref.pcgrad_weights(
+            (arena @ arena.T).cpu(), torch_ref.pcgrad_orders(
+                T, ctr, torch_ref.PCGRAD_GROUPS[name]), full=True)
+        group.flat_grad.copy_(torch_ref.pcgrad_fold(arena, w.to(arena.device)))
+        return rows.new_tensor(projected / (T * (T - 1)))
+
+    @torch.no_grad()
+    def _pcgrad_hip(self, name: str, arena: torch.Tensor, group) -> None:
+        """Two launches replace the plain arena fold of one group: Gram
+        matrix + solve, then the weighted fold into ``group.flat_grad``.
+        The arena rows must be the per-task gradients: the batch is laid out
+        task by task, row i from task ``i // (B / T)``, as the stratified
+        replay samplers produce it.  That contract is not checked here (a
+        check would be a host sync); the torch path raises on it."""
+        from ..ops import native
+        ext = native()
+        if name not in self._pcgrad_out:
+            # w[16] | visited, projected, mean cosine, share | G | orders
+            self._pcgrad_out[name] = torch.zeros(532, device=self.device)
+            if self._pcgrad_ws is None:
+                self._pcgrad_ws = torch.zeros(1 + 128 * 256,
+                                              device=self.device)
+        out = self._pcgrad_out[name]
+        T = self.num_tasks
+        ext.pcgrad_gram_solve(arena, T, 0, group.numel, self._rng_ctr,
+                              torch_ref.PCGRAD_GROUPS[name], self._pcgrad_ws,
+                              out)
+        ext.pcgrad_fold(arena, out, group.flat_grad, T, 0, group.numel)
+
+    def _pcgrad_metrics(self, out: Dict[str, torch.Tensor]):
+        """With PCGrad on, add each group's share of visited task pairs
+        that were projected: views of the solve kernel's metric slots."""
+        if self.pcgrad:
+            for name, o in self._pcgrad_out.items():
+                out[f"pcgrad_conflicts_{name}"] = \
+                    o[19] if o.numel() > 1 else o
+        return out
+
     def _row_coeff(self, states: torch.Tensor) -> torch.Tensor:
         """The loss coefficient of every row, ``[B]``: 1/B, or the
         normalized task weight / B under ``use_weighted_loss``."""
@@ -558,6 +660,7 @@ class SACEngine:
                     "truncated quantile critics: not supported together "
                     "with prioritized replay")
             self._tqc_unsupported()
+        self._pcgrad_unsupported(batch["states"].shape[0])
         out = self._update_tensors(batch)
         if per and self._per is not None:
             self.per_write_back(self._per)
@@ -594,7 +697,9 @@ class SACEngine:
                                    self.reward_scale)
 
         # --- critic step ---------------------------------------------
-        if self.tqc_M:
+        if self.pcgrad:
+            q_loss = self._pcgrad_critic_cpu(batch, y)
+        elif self.tqc_M:
             l1, l2 = torch_ref.tqc_critic_loss(
                 *self._critic_q(states, actions), y, self._row_coeff(states))
             q_loss = l1 + l2
@@ -616,7 +721,8 @@ class SACEngine:
                 alphas=self.log_alpha.exp().detach(),
                 degenerate=self.degenerate_w)
             q_loss = l1 + l2
-        q_loss.backward()
+        if not self.pcgrad:
+            q_loss.backward()
         if self.ddp is not None:
             self.ddp.allreduce_grad_(self.critic_group.flat_grad)
         self.critic_optimizer.step()
@@ -625,7 +731,15 @@ class SACEngine:
         sampled_actions, log_probs, log_stds = self._sample(states)
         q1, q2 = self._critic_q(states, sampled_actions)
         q_min = torch_ref.tqc_q(q1, q2) if self.tqc_M else torch.min(q1, q2)
-        if self.variant == "mtsac":
+        if self.pcgrad:
+            # the rows of Actor.cal_loss: its mean is the sum of these
+            rows = self._row_coeff(states) * -(
+                q_min - alpha * log_probs).reshape(-1)
+            policy_loss = rows.sum()
+            self._pcgrad_out["actor"] = self._pcgrad_cpu(
+                "actor", rows, states, self.actor_group)
+            self._pcgrad_updates += 1
+        elif self.variant == "mtsac":
             policy_loss = self.actor.cal_loss(
                 log_probs, q_min, alpha,
                 use_weighted_loss=self.use_weighted_loss, mtobss=states,
@@ -633,7 +747,8 @@ class SACEngine:
                 degenerate=self.degenerate_w)
         else:
             policy_loss = self.actor.cal_loss(log_probs, q_min, alpha)
-        policy_loss.backward()
+        if not self.pcgrad:
+            policy_loss.backward()
         if self.ddp is not None:
             self.ddp.allreduce_grad_(self.actor_group.flat_grad)
         self.actor_optimizer.step()
@@ -657,12 +772,39 @@ class SACEngine:
         # --- Polyak target update -------------------------------------
         flat_polyak_(self.target_group, self.critic_group, self.tau)
 
-        return self._clip_metrics({
+        return self._pcgrad_metrics(self._clip_metrics({
             "critic_loss": q_loss.detach(),
             "actor_loss": policy_loss.detach(),
             "alpha_loss": loss_log_alpha.detach(),
             "entropy": entropy.detach(),
-        })
+        }))
+
+    def _pcgrad_critic_cpu(self, batch, y):
+        """The critic loss of the torch path as per-row terms (the losses
+        of the default path are their sums), surgered into the critic's
+        flat gradient.  Returns the loss."""
+        states = batch["states"]
+        coeff = self._row_coeff(states)
+        q1, q2 = self._critic_q(states, batch["actions"])
+        if self.tqc_M:
+            # tqc_critic_loss sums coeff * rho_row: one row at a time
+            eye = torch.eye(states.shape[0], dtype=coeff.dtype,
+                            device=coeff.device)
+            rows = torch.stack([sum(torch_ref.tqc_critic_loss(
+                q1, q2, y, coeff * e)) for e in eye])
+        else:
+            d1, d2 = y - q1, y - q2
+            if "is_weights" in batch:
+                w = batch["is_weights"].reshape(-1)
+                coeff = coeff * (w / w.max())
+                self.per_indices = batch["indices"]
+                self.per_new_priorities = torch_ref.per_new_priorities(
+                    d1.detach(), d2.detach(), *self._per_params())
+                self._per_zeroed = False
+            rows = coeff * (d1 ** 2 + d2 ** 2).reshape(-1)
+        self._pcgrad_out["critic"] = self._pcgrad_cpu(
+            "critic", rows, states, self.critic_group)
+        return rows.sum().detach()
 
     def _actor_weights(self):
         if self.variant in ("sac", "vsac"):
@@ -682,9 +824,19 @@ class SACEngine:
         one reduce per layer).  chunk targets ~8 batch splits, rounded to
         the 64-row GEMM tile."""
         store = self._dw_arenas
-        key = (name, numel, B)
+        # PCGrad: one arena row per task (S = T, B / T rows each), so row t
+        # is the gradient of task t's share of the loss; keyed apart from
+        # the default mode's buffer
+        per_task = self.pcgrad and name in ("critic", "actor")
+        key = (name, numel, B, "per-task") if per_task else (name, numel, B)
         if key not in store:
-            if name.endswith("@rowblocks"):
+            if per_task:
+                # rows padded to 16 bytes: the Gram and fold kernels then
+                # move float4s (the pad columns are never read)
+                S = self.num_tasks
+                chunk = B // S
+                numel = (numel + 3) // 4 * 4
+            elif name.endswith("@rowblocks"):
                 # one arena row per 64-row block (fused narrow backward)
                 S = (B + 63) // 64
                 chunk = 64
@@ -803,8 +955,10 @@ class SACEngine:
         self._critic_chain.backward(dy, acts_c, arena_c, S_c, ch_c)
         # single-GPU: the critic Adam kernel folds the arena itself; with
         # DP the all-reduce needs the folded gradient first
-        fold_c = self._fuse_tail and self.ddp is None
-        if not fold_c:
+        fold_c = self._fuse_tail and self.ddp is None and not self.pcgrad
+        if self.pcgrad:
+            self._pcgrad_hip("critic", arena_c, self.critic_group)
+        elif not fold_c:
             ext.reduce_arena(arena_c, self.critic_group.flat_grad, S_c)
         self._dp_st = {
             "arena_c": (arena_c, S_c) if fold_c else None,
@@ -953,8 +1107,10 @@ class SACEngine:
                                             self.actor_group.numel, B)
         self._actor_chain.backward(dhead, st["acts_a"], arena_a, S_a, ch_a,
                                    rows=slice(B, None))
-        fold_a = fuse and self.ddp is None
-        if not fold_a:
+        fold_a = fuse and self.ddp is None and not self.pcgrad
+        if self.pcgrad:
+            self._pcgrad_hip("actor", arena_a, self.actor_group)
+        elif not fold_a:
             ext.reduce_arena(arena_a, fg_a, S_a)
         st["arena_a"] = (arena_a, S_a) if fold_a else None
         st["al"] = al
@@ -977,12 +1133,12 @@ class SACEngine:
         # ~5 µs kernel every captured step just for bookkeeping
         self._update_targets()
         closs, al = st["closs"], st["al"]
-        return self._clip_metrics({
+        return self._pcgrad_metrics(self._clip_metrics({
             "critic_loss": closs[6],  # summed in-kernel
             "actor_loss": al[0],
             "alpha_loss": al[2],
             "entropy": al[3],
-        })
+        }))
 
     def _polyak_args(self):
         return (self.target_group, self.critic_group, self.tau,

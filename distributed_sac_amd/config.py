@@ -120,6 +120,11 @@ class SACConfig:
     # target.  See docs/KERNELS.md "Truncated quantile critics".
     critic_quantiles: Optional[int] = None
     critic_quantiles_drop: Optional[int] = None
+    # net-new (the reference has none): PCGrad gradient surgery between the
+    # per-task gradients of the critic and of the actor (mtsac only).  None
+    # (a cfg without the key): DSAC_PCGRAD=1, else off.  See docs/KERNELS.md
+    # "PCGrad".
+    pcgrad: Optional[bool] = None
     # CARE-only block (reference cfg "encoder"):
     encoder: Optional[Dict[str, Any]] = None
     use_modified_care: bool = False
@@ -181,6 +186,17 @@ class SACConfig:
                     raise ValueError(f"{env} must be an integer, got {s!r}")
             vals.append(v)
         return check_critic_quantiles(*vals)
+
+    @property
+    def pcgrad_choice(self) -> bool:
+        """The cfg's ``pcgrad`` where set, else ``DSAC_PCGRAD`` (``1`` = on;
+        unset, empty or ``0`` = off)."""
+        if self.pcgrad is not None:
+            return bool(self.pcgrad)
+        env = os.environ.get("DSAC_PCGRAD", "")
+        if env not in ("", "0", "1"):
+            raise ValueError(f"DSAC_PCGRAD must be 0 or 1, got {env!r}")
+        return env == "1"
 
     @property
     def per_kwargs(self) -> Dict[str, Any]:
@@ -261,6 +277,11 @@ class SACConfig:
             check_critic_quantiles(
                 c.critic_quantiles, 2 if c.critic_quantiles_drop is None
                 else c.critic_quantiles_drop)
+        if "pcgrad" in cfg:
+            if not isinstance(cfg["pcgrad"], bool):
+                raise ValueError(
+                    f"pcgrad must be true or false, got {cfg['pcgrad']!r}")
+            c.pcgrad = cfg["pcgrad"]
         if "use_modified_care" in cfg:
             c.use_modified_care = bool(cfg["use_modified_care"])
         if "encoder" in cfg:

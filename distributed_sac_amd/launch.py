@@ -63,6 +63,10 @@ def main():
                          "pooled target (default: the cfg's "
                          "critic_quantiles_drop, else "
                          "DSAC_CRITIC_QUANTILES_DROP, else 2)")
+    ap.add_argument("--pcgrad", action="store_true", default=None,
+                    help="PCGrad gradient surgery between the per-task "
+                         "critic and actor gradients, mtsac only (default: "
+                         "the cfg's pcgrad, else DSAC_PCGRAD, else off)")
     # eval mode
     ap.add_argument("--eval", action="store_true")
     ap.add_argument("--checkpoint", default=None)
@@ -86,7 +90,10 @@ def main():
         cfg.critic_quantiles = args.critic_quantiles
     if args.critic_quantiles_drop is not None:
         cfg.critic_quantiles_drop = args.critic_quantiles_drop
+    if args.pcgrad:
+        cfg.pcgrad = True
     cfg.critic_quantiles_choice   # validate before anything starts
+    cfg.pcgrad_choice
 
     env_fn = default_env_fn
     if args.env:

@@ -1224,3 +1224,89 @@ def actor_alpha_loss_oracle(aq1, aq2, lp, ls, states, log_alpha, T: int,
         mag = torch.zeros(n, dtype=torch.float64).index_add_(0, t, term.abs())
         res.update(dla=dla, tol_dla=(nr + L_dla + 2) * SQ_U * mag)
     return res
+
+
+# ---------------------------------------------------------------------------
+# PCGrad gradient surgery (Yu et al., 2020) in coefficient space
+# (docs/KERNELS.md "PCGrad"): the CPU path and the oracle of
+# k_pcgrad_gram_solve / k_pcgrad_fold.  Every projected gradient is a linear
+# combination of the task gradients g_t, so the algorithm runs on the T x T
+# Gram matrix G = g g^T alone and its result is sum_t w_t g_t.
+# ---------------------------------------------------------------------------
+
+PCGRAD_MAX_T = 16
+PCGRAD_GROUPS = {"critic": 0, "actor": 1}     # salt of the visiting orders
+
+
+@torch.no_grad()
+def pcgrad_orders(T: int, ctr, group: int) -> torch.Tensor:
+    """int64 ``[T, T - 1]``: row i lists the tasks j != i in the order task
+    i visits them — ascending ``sm64(ctr * 0x100000001 + 2^63 + 256 +
+    256 group + 16 i + j)`` compared as unsigned words, ties by j.  ``ctr``
+    is the rng counter (int or one-element tensor)."""
+    if not 2 <= T <= PCGRAD_MAX_T:
+        raise ValueError(f"pcgrad: num_tasks must be in 2..{PCGRAD_MAX_T}, "
+                         f"got {T}")
+    c = int(ctr.reshape(-1)[0]) if torch.is_tensor(ctr) else int(ctr)
+    c = torch.tensor(_i64(c), dtype=torch.int64)
+    i = torch.arange(T, dtype=torch.int64)[:, None]
+    j = torch.arange(T, dtype=torch.int64)[None, :]
+    key = _sm64(c * 0x100000001 + _i64(1 << 63) + 256 + 256 * int(group)
+                + 16 * i + j)
+    key = key ^ _i64(1 << 63)          # signed order of these = unsigned order
+    js = j.expand(T, T)[i != j].reshape(T, T - 1)
+    ks = key[(i != j).expand(T, T)].reshape(T, T - 1)
+    return torch.gather(js, 1, torch.sort(ks, dim=1, stable=True).indices)
+
+
+@torch.no_grad()
+def pcgrad_weights(G: torch.Tensor, orders: torch.Tensor,
+                   full: bool = False):
+    """The PCGrad solve on the Gram matrix ``G [T, T]``, in its dtype.
+    ``a_i = e_i``; for j in ``orders[i]``: ``d = sum_k a_i[k] G[k][j]``
+    (k ascending), and if ``d < 0`` and ``G[j][j] > 0`` then
+    ``a_i[j] -= d / G[j][j]``.  Returns ``w [T]`` with ``w[t] = sum_i
+    a_i[t]`` (i ascending); with ``full`` also the coefficients ``a [T, T]``
+    and the number of projected pairs (T (T - 1) are visited)."""
+    T = G.shape[0]
+    a = torch.eye(T, dtype=G.dtype)
+    projected = 0
+    for i in range(T):
+        for j in orders[i].tolist():
+            d = G.new_zeros(())
+            for k in range(T):
+                d = d + a[i, k] * G[k, j]
+            if bool(d < 0) and bool(G[j, j] > 0):
+                a[i, j] = a[i, j] - d / G[j, j]
+                projected += 1
+    w = G.new_zeros(T)
+    for i in range(T):
+        w = w + a[i]
+    return (w, a, projected) if full else w
+
+
+@torch.no_grad()
+def pcgrad_fold(arena: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """``sum_t w[t] * arena[t]`` added in t order from zero."""
+    out = torch.zeros_like(arena[0])
+    for t in range(w.shape[0]):
+        out = out + w[t].to(arena.dtype) * arena[t]
+    return out
+
+
+def pcgrad_task_rows(one_hots: torch.Tensor, T: int) -> int:
+    """Rows per task of a stratified batch; raises unless row i of the
+    one-hot block belongs to task ``i // (B / T)`` (the layout of the
+    stratified replay samplers, which the per-task arena relies on)."""
+    B = one_hots.shape[0]
+    if B % T:
+        raise NotImplementedError(
+            f"pcgrad: the batch ({B} rows) must divide into num_tasks = {T} "
+            "equal parts (B % T != 0)")
+    per = B // T
+    want = torch.arange(B, device=one_hots.device) // per
+    if not torch.equal(one_hots[:, -T:].argmax(dim=1), want):
+        raise ValueError(
+            "pcgrad: batch rows must be laid out task by task, row i from "
+            "task i // (B / T) (the stratified replay samplers' layout)")
+    return per

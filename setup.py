@@ -28,7 +28,8 @@ setup(
                      "distributed_sac_amd/ops/_hip/chain_gemm.hip",
                      "distributed_sac_amd/ops/_hip/f32_chain.hip",
                      "distributed_sac_amd/ops/_hip/f32_chain_bwd.hip",
-                     "distributed_sac_amd/ops/_hip/tqc.hip"],
+                     "distributed_sac_amd/ops/_hip/tqc.hip",
+                     "distributed_sac_amd/ops/_hip/pcgrad.hip"],
             extra_compile_args={
                 "cxx": ["-O3"],
                 "nvcc": ["-O3", "--offload-arch=gfx950"],
