@@ -12,7 +12,6 @@ instead of one per elementwise op — the backward chain is hand-written HIP.
 from __future__ import annotations
 
 import os
-from types import SimpleNamespace
 from typing import List, Optional, Sequence
 
 import torch
@@ -135,113 +134,112 @@ def _f32_chain_bwd(dy, acts, ws, G: int, dx0_lo: int, need_w):
     return dx0, dws, dbs
 
 
-def _cat_backward(base, ctx, *grads):
-    """Backward of a two-input ([x1 || x2]) chain forward: ``base``'s
-    backward on the single-input argument layout, its dx split by column."""
-    nig = ctx.needs_input_grad
-    shim = SimpleNamespace(
-        n_layers=ctx.n_layers, saved_tensors=ctx.saved_tensors,
-        grad_row_start=getattr(ctx, "grad_row_start", 0),
-        dx0_lo=0 if nig[0] else ctx.c1,
-        needs_input_grad=(nig[0] or nig[1],) + tuple(nig[2:]))
-    dx, *rest = base.backward(shim, *grads)
-    c1 = ctx.c1
-    if dx is not None and not nig[0]:
-        # the chain backward skipped x1's columns, the per-layer one did not
-        c1 -= ctx.saved_tensors[ctx.n_layers + 1].shape[-1] - dx.shape[1]
-    return (dx[:, :c1] if nig[0] else None,
-            dx[:, c1:] if nig[1] else None, *rest)
-
-
 # ---------------------------------------------------------------------------
-# Fused MLP (Linear+bias+ReLU chain, linear output layer)
+# Fused fp32 MLP (Linear+bias+ReLU chain, linear output layer), G stacked
+# networks per launch (grouped GEMMs; the twin critic is G=2 with weights
+# [2,N,K] — views into the critic's flat parameter buffer)
 # ---------------------------------------------------------------------------
 
-class _FusedMLP(torch.autograd.Function):
-    """Whole-MLP fused forward/backward on HIP.
+class _MLPF32(torch.autograd.Function):
+    """Whole-MLP fused forward/backward on HIP, for G networks at once.
 
     forward saves post-activation intermediates; ReLU backward masks come
     from the outputs themselves (relu(y)==0 <=> grad 0).
+
+    Layer 0 consumes the shared x (group-stride 0); later layers run on
+    per-group activations [G,B,N].  Backward mirrors this: per-group dX for
+    hidden layers, group-SUMMED dX at layer 0 (both Qs consume the same x —
+    reference Critic.forward computes Q1(x), Q2(x) on one cat([s,a])).
+    G == 1 has no group dimension anywhere, and for it both dX modes are
+    the same launch.  G > 1 returns one output per head, so autograd hands
+    backward one gradient per head and backward stacks them itself.
+
+    x2 is not None: the input is [x || x2], concatenated by the chain
+    kernel's loader (which also saves the concatenation for backward) —
+    the caller has checked _f32_chain_ok.
     """
 
     @staticmethod
-    def forward(ctx, x: torch.Tensor, n_layers: int, grad_row_start: int,
-                *wb):
-        ws = wb[:n_layers]
-        bs = wb[n_layers:]
+    def forward(ctx, x: torch.Tensor, x2: Optional[torch.Tensor],
+                n_layers: int, G: int, grad_row_start: int, *wb):
+        ws = wb[:n_layers]      # each [N, K], or [G, N, K]
+        bs = wb[n_layers:]      # each [N], or [G, N]
         ext = native()
-        if _f32_chain_ok(x, None, ws, bs, 1):
-            h, saved = ext.mlp_chain_fwd_f32(x, None, list(ws), list(bs),
-                                             1, True)
+        if x2 is not None or _f32_chain_ok(x, None, ws, bs, G):
+            h, saved = ext.mlp_chain_fwd_f32(x, x2, list(ws), list(bs),
+                                             G, True)
             acts: List[torch.Tensor] = [*saved, h]
         else:
             acts = [x]
-            h = x
             for i in range(n_layers):
                 act = ACT_RELU if i < n_layers - 1 else ACT_NONE
-                h = ext.linear_act_fwd(h, ws[i], bs[i], act)
-                acts.append(h)
+                acts.append(ext.linear_act_fwd_g(acts[-1], ws[i], bs[i],
+                                                 act, G))
+            h = acts[-1]
         ctx.save_for_backward(*acts, *ws)
         ctx.n_layers = n_layers
+        ctx.G = G
         ctx.grad_row_start = grad_row_start
-        return h
+        ctx.c1 = x.shape[1]
+        return h if G == 1 else tuple(h[g] for g in range(G))
 
     @staticmethod
-    def backward(ctx, grad_out: torch.Tensor):
-        n = ctx.n_layers
+    def backward(ctx, *grads: torch.Tensor):
+        n, G = ctx.n_layers, ctx.G
         saved = ctx.saved_tensors
         acts = saved[: n + 1]
         ws = saved[n + 1:]
         ext = native()
+        # forward args: (x, x2, n_layers, G, grad_row_start, *ws, *bs)
+        need_x1, need_x2 = ctx.needs_input_grad[:2]
+        need_w = ctx.needs_input_grad[-2 * n:-n]
+        dy = grads[0] if G == 1 else torch.stack(grads, dim=0)  # [G,B,Nout]
         # rows below grad_row_start carry no gradient by construction (the
         # batched TD-side forward): slice them out of the backward chain
-        # (row slices of row-major tensors stay contiguous)
+        # (row slices of row-major 2-D tensors stay contiguous)
         r0 = ctx.grad_row_start
         if r0:
-            acts = [a[r0:] for a in acts]
-            grad_out = grad_out[r0:]
-        dy = grad_out.contiguous()
-        if _f32_chain_bwd_ok(dy, acts[:n], ws, 1):
-            dx, dws, dbs = _f32_chain_bwd(
-                dy, acts[:n], ws, 1,
-                getattr(ctx, "dx0_lo", 0) if ctx.needs_input_grad[0] else -1,
-                ctx.needs_input_grad[3:3 + n])
-            return (dx, None, None, *dws, *dbs)
-        dws: List[Optional[torch.Tensor]] = [None] * n
-        dbs: List[Optional[torch.Tensor]] = [None] * n
-        for i in range(n - 1, -1, -1):
-            # mask==1 only for hidden layers (their saved act is post-ReLU)
-            act = ACT_RELU if i < n - 1 else ACT_NONE
-            if ctx.needs_input_grad[3 + i]:
-                dw, db = ext.linear_bwd_dwdb(dy, acts[i], acts[i + 1], act)
-                dws[i], dbs[i] = dw, db
-            if i > 0:
-                dy = ext.linear_bwd_dx(dy, ws[i], acts[i + 1], act)
-        dx = ext.linear_bwd_dx(dy, ws[0], acts[1],
-                               ACT_RELU if n > 1 else ACT_NONE) \
-            if ctx.needs_input_grad[0] else None
-        return (dx, None, None, *dws, *dbs)
+            acts = [a[..., r0:, :] for a in acts]
+            dy = dy[..., r0:, :]
+        dy = dy.contiguous()
+        c1 = ctx.c1             # dx[:, :c1] is x's gradient, the rest x2's
+        dx = None
+        if _f32_chain_bwd_ok(dy, acts[:n], ws, G):
+            # only x2 needs a gradient: the dx walk skips x's columns
+            lo = 0 if need_x1 else c1 if need_x2 else -1
+            dx, dws, dbs = _f32_chain_bwd(dy, acts[:n], ws, G, lo, need_w)
+            c1 -= max(lo, 0)
+        else:
+            dws, dbs = [None] * n, [None] * n
+            for i in range(n - 1, -1, -1):
+                # mask==1 only for hidden layers (their saved act is
+                # post-ReLU)
+                act = ACT_RELU if i < n - 1 else ACT_NONE
+                if need_w[i]:
+                    dws[i], dbs[i] = ext.linear_bwd_dwdb_g(
+                        dy, acts[i], acts[i + 1], act, G)
+                if i > 0:
+                    dy = ext.linear_bwd_dx_g(dy, ws[i], acts[i + 1], act,
+                                             G, 0)
+                elif need_x1 or need_x2:
+                    dx = ext.linear_bwd_dx_g(dy, ws[0], acts[1], act, G, 1)
+        return (dx[:, :c1] if need_x1 else None,
+                dx[:, c1:] if need_x2 else None, None, None, None,
+                *dws, *dbs)
 
 
-class _FusedMLPCat(torch.autograd.Function):
-    """_FusedMLP on x = [x1 || x2], concatenated by the chain kernel's
-    loader (which also saves the concatenation for backward)."""
-
-    @staticmethod
-    def forward(ctx, x1, x2, n_layers: int, grad_row_start: int, *wb):
-        ws = wb[:n_layers]
-        bs = wb[n_layers:]
-        h, saved = native().mlp_chain_fwd_f32(x1, x2, list(ws), list(bs),
-                                              1, True)
-        ctx.save_for_backward(*saved, h, *ws)
-        ctx.n_layers = n_layers
-        ctx.grad_row_start = grad_row_start
-        ctx.c1 = x1.shape[1]
-        return h
-
-    @staticmethod
-    def backward(ctx, grad_out: torch.Tensor):
-        return _cat_backward(_FusedMLP, ctx, grad_out)
+def _mlp_f32(x, x2, ws, bs, G: int, grad_row_start: int):
+    """_MLPF32 on [x || x2].  x2 reaches it only when the chain-forward
+    kernel takes the call; otherwise torch.cat joins the two out here, and
+    autograd's own cat-backward splits the gradient.  A chain forward
+    nobody differentiates returns the stacked [G,B,Nout] (indexable like
+    the Function's tuple of heads)."""
+    if _f32_chain_ok(x, x2, ws, bs, G):
+        if not torch.is_grad_enabled():
+            return _f32_chain_nograd(x, x2, ws, bs, G)
+    elif x2 is not None:
+        x, x2 = torch.cat([x, x2], dim=-1), None
+    return _MLPF32.apply(x, x2, len(ws), G, grad_row_start, *ws, *bs)
 
 
 def mlp_forward(x: torch.Tensor,
@@ -257,19 +255,19 @@ def mlp_forward(x: torch.Tensor,
 
     x2: the MLP's input is [x || x2] (columns)."""
     if _use_native(x):
-        if _f32_chain_ok(x, x2, weights, biases, 1):
-            if not torch.is_grad_enabled():
-                return _f32_chain_nograd(x, x2, weights, biases, 1)
-            if x2 is not None:
-                return _FusedMLPCat.apply(x, x2, len(weights),
-                                          grad_row_start, *weights, *biases)
-        elif x2 is not None:
-            x = torch.cat([x, x2], dim=-1)
-        return _FusedMLP.apply(x, len(weights), grad_row_start,
-                               *weights, *biases)
+        return _mlp_f32(x, x2, weights, biases, 1, grad_row_start)
     if x2 is not None:
         x = torch.cat([x, x2], dim=-1)
     return torch_ref.mlp_forward(x, weights, biases)
+
+
+def twin_mlp_forward(x: torch.Tensor, stacked_ws, stacked_bs,
+                     x2: Optional[torch.Tensor] = None):
+    """Both Q heads in one grouped launch per layer.  stacked_ws[i] is a
+    [2,N,K] view into the critic flat parameter buffer.  x2: the input is
+    [x || x2] (columns)."""
+    q = _mlp_f32(x, x2, stacked_ws, stacked_bs, 2, 0)
+    return q[0], q[1]
 
 
 # ---------------------------------------------------------------------------
@@ -308,108 +306,6 @@ def squashed_gaussian(mu: torch.Tensor, log_std_raw: torch.Tensor,
     if _use_native(mu):
         return _SquashedGaussian.apply(mu, log_std_raw, eps, k)
     return torch_ref.squashed_gaussian(mu, log_std_raw, eps, k)
-
-
-# ---------------------------------------------------------------------------
-# Fused twin-MLP (grouped GEMMs: both Q networks in one launch per layer,
-# stacked weights [2,N,K] — views into the critic's flat parameter buffer)
-# ---------------------------------------------------------------------------
-
-class _FusedTwinMLP(torch.autograd.Function):
-    """Twin-Q MLP: q1,q2 from shared x through stacked weights [2,N,K].
-
-    Layer 0 consumes the shared x (group-stride 0); later layers run on
-    per-group activations [2,B,N].  Backward mirrors this: per-group dX for
-    hidden layers, group-SUMMED dX at layer 0 (both Qs consume the same x —
-    reference Critic.forward computes Q1(x), Q2(x) on one cat([s,a])).
-    """
-
-    @staticmethod
-    def forward(ctx, x: torch.Tensor, n_layers: int, *wb):
-        ws = wb[:n_layers]      # each [2, N, K]
-        bs = wb[n_layers:]      # each [2, N]
-        ext = native()
-        if _f32_chain_ok(x, None, ws, bs, 2):
-            h, saved = ext.mlp_chain_fwd_f32(x, None, list(ws), list(bs),
-                                             2, True)
-            acts = [*saved, h]
-        else:
-            acts = [x]
-            h = x
-            for i in range(n_layers):
-                act = ACT_RELU if i < n_layers - 1 else ACT_NONE
-                h = ext.linear_act_fwd_g(h, ws[i], bs[i], act, 2)
-                acts.append(h)
-        ctx.save_for_backward(*acts, *ws)
-        ctx.n_layers = n_layers
-        return h[0], h[1]
-
-    @staticmethod
-    def backward(ctx, dq1: torch.Tensor, dq2: torch.Tensor):
-        n = ctx.n_layers
-        saved = ctx.saved_tensors
-        acts = saved[: n + 1]
-        ws = saved[n + 1:]
-        ext = native()
-        dy = torch.stack([dq1, dq2], dim=0).contiguous()  # [2,B,Nout]
-        if _f32_chain_bwd_ok(dy, acts[:n], ws, 2):
-            dx, dws, dbs = _f32_chain_bwd(
-                dy, acts[:n], ws, 2,
-                getattr(ctx, "dx0_lo", 0) if ctx.needs_input_grad[0] else -1,
-                ctx.needs_input_grad[2:2 + n])
-            return (dx, None, *dws, *dbs)
-        dws = [None] * n
-        dbs = [None] * n
-        for i in range(n - 1, -1, -1):
-            act = ACT_RELU if i < n - 1 else ACT_NONE
-            if ctx.needs_input_grad[2 + i]:
-                dw, db = ext.linear_bwd_dwdb_g(dy, acts[i], acts[i + 1],
-                                               act, 2)
-                dws[i], dbs[i] = dw, db
-            if i > 0:
-                dy = ext.linear_bwd_dx_g(dy, ws[i], acts[i + 1], act, 2, 0)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = ext.linear_bwd_dx_g(dy, ws[0], acts[1],
-                                     ACT_RELU if n > 1 else ACT_NONE, 2, 1)
-        return (dx, None, *dws, *dbs)
-
-
-class _FusedTwinMLPCat(torch.autograd.Function):
-    """_FusedTwinMLP on x = [x1 || x2] ([states || actions]), concatenated
-    by the chain kernel's loader."""
-
-    @staticmethod
-    def forward(ctx, x1, x2, n_layers: int, *wb):
-        ws = wb[:n_layers]
-        bs = wb[n_layers:]
-        h, saved = native().mlp_chain_fwd_f32(x1, x2, list(ws), list(bs),
-                                              2, True)
-        ctx.save_for_backward(*saved, h, *ws)
-        ctx.n_layers = n_layers
-        ctx.c1 = x1.shape[1]
-        return h[0], h[1]
-
-    @staticmethod
-    def backward(ctx, dq1: torch.Tensor, dq2: torch.Tensor):
-        return _cat_backward(_FusedTwinMLP, ctx, dq1, dq2)
-
-
-def twin_mlp_forward(x: torch.Tensor, stacked_ws, stacked_bs,
-                     x2: Optional[torch.Tensor] = None):
-    """Both Q heads in one grouped launch per layer.  stacked_ws[i] is a
-    [2,N,K] view into the critic flat parameter buffer.  x2: the input is
-    [x || x2] (columns)."""
-    if _f32_chain_ok(x, x2, stacked_ws, stacked_bs, 2):
-        if not torch.is_grad_enabled():
-            h = _f32_chain_nograd(x, x2, stacked_ws, stacked_bs, 2)
-            return h[0], h[1]
-        if x2 is not None:
-            return _FusedTwinMLPCat.apply(x, x2, len(stacked_ws),
-                                          *stacked_ws, *stacked_bs)
-    elif x2 is not None:
-        x = torch.cat([x, x2], dim=-1)
-    return _FusedTwinMLP.apply(x, len(stacked_ws), *stacked_ws, *stacked_bs)
 
 
 # ---------------------------------------------------------------------------
@@ -564,168 +460,93 @@ attention_pool = torch_ref.attention_pool
 # dW/db accumulate into the flat fp32 gradient buffers.
 # ---------------------------------------------------------------------------
 
-class _FusedMLPBF16(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x: torch.Tensor, n_layers: int, grad_row_start: int,
-                ws_bf16, *wb_f32):
-        ext = native()
-        bs = wb_f32[n_layers:]
-        xh = x.to(torch.bfloat16)
-        acts = [xh]
-        h = xh
-        for i in range(n_layers):
-            last = i == n_layers - 1
-            act = ACT_NONE if last else ACT_RELU
-            h = ext.linear_act_fwd_bf16(h, ws_bf16[i], bs[i].contiguous(),
-                                        act, 1, 1 if last else 0)
-            acts.append(h)
-        ctx.save_for_backward(*acts[:-1])
-        ctx.ws_bf16 = ws_bf16
-        ctx.n_layers = n_layers
-        ctx.grad_row_start = grad_row_start
-        return h  # fp32
+class _MLPBF16(torch.autograd.Function):
+    """Whole-MLP fused forward/backward on the bf16 GEMM kernels, for G
+    networks at once (grid.z = G).  Layer 0 consumes the shared x; later
+    layers run per group on [G,B,*]; the output is fp32.  As in _MLPF32,
+    G == 1 has no group dimension and the layer-0 dX is summed over the
+    groups.  The ReLU masks come from the saved bf16 hidden outputs.
 
-    @staticmethod
-    def backward(ctx, grad_out: torch.Tensor):
-        n = ctx.n_layers
-        acts = list(ctx.saved_tensors)  # bf16: input + hidden outputs
-        ws = ctx.ws_bf16
-        ext = native()
-        r0 = ctx.grad_row_start
-        if r0:
-            acts = [a[r0:] for a in acts]
-            grad_out = grad_out[r0:]
-        dy = grad_out.contiguous().to(torch.bfloat16)
-        dws = [None] * n
-        dbs = [None] * n
-        for i in range(n - 1, -1, -1):
-            act = ACT_RELU if i < n - 1 else ACT_NONE
-            yout = acts[i + 1] if i < n - 1 else acts[i]  # dummy when act=0
-            dw, db = ext.linear_bwd_dwdb_bf16(dy, acts[i], yout, act, 1)
-            dws[i], dbs[i] = dw, db
-            if i > 0:
-                dy = ext.linear_bwd_dx_bf16(dy, ws[i], yout, act, 1, 1)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = ext.linear_bwd_dx_bf16(
-                dy, ws[0], acts[1] if n > 1 else acts[0],
-                ACT_RELU if n > 1 else ACT_NONE, 1, 1).to(torch.float32)
-        return (dx, None, None, None, *dws, *dbs)
-
-
-def mlp_forward_bf16(x, ws_f32, bs_f32, ws_bf16, grad_row_start: int = 0):
-    return _FusedMLPBF16.apply(x, len(ws_f32), grad_row_start,
-                               tuple(ws_bf16), *ws_f32, *bs_f32)
-
-
-class _FusedTwinMLPBF16(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x: torch.Tensor, n_layers: int, ws_bf16, *wb_f32):
-        ext = native()
-        bs = wb_f32[n_layers:]
-        xh = x.to(torch.bfloat16)
-        acts = [xh]
-        h = xh
-        for i in range(n_layers):
-            last = i == n_layers - 1
-            act = ACT_NONE if last else ACT_RELU
-            h = ext.linear_act_fwd_bf16(h, ws_bf16[i], bs[i].contiguous(),
-                                        act, 2, 1 if last else 0)
-            acts.append(h)
-        ctx.save_for_backward(*acts[:-1])
-        ctx.ws_bf16 = ws_bf16
-        ctx.n_layers = n_layers
-        return h[0], h[1]  # fp32 [B, 1] each
-
-    @staticmethod
-    def backward(ctx, dq1, dq2):
-        n = ctx.n_layers
-        acts = list(ctx.saved_tensors)
-        ws = ctx.ws_bf16
-        ext = native()
-        dy = torch.stack([dq1, dq2], dim=0).contiguous().to(torch.bfloat16)
-        dws = [None] * n
-        dbs = [None] * n
-        for i in range(n - 1, -1, -1):
-            act = ACT_RELU if i < n - 1 else ACT_NONE
-            yout = acts[i + 1] if i < n - 1 else acts[i]
-            # forward args: (x, n_layers, ws_bf16_tuple, *ws_f32, *bs_f32)
-            # -> ws_f32[i] is input index 3+i (the non-tensor tuple at 2
-            # always reports False — indexing 2+i silently skipped layer
-            # 0's dW)
-            if ctx.needs_input_grad[3 + i]:
-                dw, db = ext.linear_bwd_dwdb_bf16(dy, acts[i], yout, act, 2)
-                dws[i], dbs[i] = dw, db
-            if i > 0:
-                dy = ext.linear_bwd_dx_bf16(dy, ws[i], yout, act, 2, 0)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = ext.linear_bwd_dx_bf16(
-                dy, ws[0], acts[1] if n > 1 else acts[0],
-                ACT_RELU if n > 1 else ACT_NONE, 2, 1).to(torch.float32)
-        return (dx, None, None, *dws, *dbs)
-
-
-def twin_mlp_forward_bf16(x, stacked_ws_f32, stacked_bs_f32, ws_bf16):
-    return _FusedTwinMLPBF16.apply(x, len(ws_bf16), tuple(ws_bf16),
-                                   *stacked_ws_f32, *stacked_bs_f32)
-
-
-class _GroupedMLPBF16(torch.autograd.Function):
-    """CARE mixture-of-k-encoders as grouped bf16 GEMMs (grid.z = k).
-
-    Weights are the reference's batched-Linear parameters W (k,in,out) /
-    b (k,1,out) (state_encoder.Linear); compute uses TRANSPOSED bf16
-    mirrors (k,out,in) matching the GEMM kernel's [G,N,K] layout.  Layer 0
-    consumes shared x; later layers per-group [k,B,*].  Output [k,B,out]
-    fp32.  Backward runs full-batch (upstream grads are zero outside the
-    grad-carrying rows; the mixture layers are 50-wide — cheaper than
-    slicing per-group activations contiguous).
+    transposed: the CARE mixture of k encoders.  The fp32 parameters are
+    the reference's batched-Linear W (k,in,out) / b (k,1,out)
+    (state_encoder.Linear); compute uses TRANSPOSED bf16 mirrors (k,out,in)
+    matching the GEMM kernel's [G,N,K] layout, so dW goes back permuted.
+    Its consumer weighs the stacked [k,B,out] as one tensor; the twin
+    critic (G > 1, not transposed) returns one output per head.  The
+    mixture's backward runs full-batch (grad_row_start=0: upstream grads
+    are zero outside the grad-carrying rows; the mixture layers are 50-wide
+    — cheaper than slicing per-group activations contiguous).
     """
 
     @staticmethod
-    def forward(ctx, x: torch.Tensor, n_layers: int, k: int, ws_bf16T,
-                *wb_f32):
+    def forward(ctx, x: torch.Tensor, n_layers: int, G: int,
+                grad_row_start: int, transposed: bool, ws_bf16, *wb_f32):
         ext = native()
         bs = wb_f32[n_layers:]
-        xh = x.to(torch.bfloat16)
-        acts = [xh]
-        h = xh
+        acts = [x.to(torch.bfloat16)]
         for i in range(n_layers):
             last = i == n_layers - 1
-            h = ext.linear_act_fwd_bf16(
-                h, ws_bf16T[i], bs[i].view(k, -1).contiguous(),
-                0 if last else 1, k, 1 if last else 0)
-            acts.append(h)
-        ctx.save_for_backward(*acts[:-1])
-        ctx.ws_bf16T = ws_bf16T
+            b = bs[i].view(G, -1) if transposed else bs[i]
+            acts.append(ext.linear_act_fwd_bf16(
+                acts[-1], ws_bf16[i], b.contiguous(),
+                ACT_NONE if last else ACT_RELU, G, 1 if last else 0))
+        h = acts.pop()          # fp32
+        ctx.save_for_backward(*acts)     # bf16: input + hidden outputs
+        ctx.ws_bf16 = ws_bf16
         ctx.n_layers = n_layers
-        ctx.k = k
-        return h
+        ctx.G = G
+        ctx.grad_row_start = grad_row_start
+        ctx.transposed = transposed
+        if G == 1 or transposed:
+            return h
+        return tuple(h[g] for g in range(G))
 
     @staticmethod
-    def backward(ctx, grad_out: torch.Tensor):
-        n, k = ctx.n_layers, ctx.k
+    def backward(ctx, *grads: torch.Tensor):
+        n, G = ctx.n_layers, ctx.G
         acts = list(ctx.saved_tensors)
-        ws = ctx.ws_bf16T
+        ws = ctx.ws_bf16
         ext = native()
-        dy = grad_out.contiguous().to(torch.bfloat16)
-        dws = [None] * n
-        dbs = [None] * n
+        # forward args: (x, n_layers, G, grad_row_start, transposed,
+        # ws_bf16, *ws_f32, *bs_f32) — the non-tensor arguments always
+        # report False, so the weights are counted from the end
+        need_w = ctx.needs_input_grad[-2 * n:-n]
+        dy = grads[0] if len(grads) == 1 else torch.stack(grads, dim=0)
+        r0 = ctx.grad_row_start
+        if r0:
+            acts = [a[..., r0:, :] for a in acts]
+            dy = dy[..., r0:, :]
+        dy = dy.contiguous().to(torch.bfloat16)
+        dx = None
+        dws: List[Optional[torch.Tensor]] = [None] * n
+        dbs: List[Optional[torch.Tensor]] = [None] * n
         for i in range(n - 1, -1, -1):
             act = ACT_RELU if i < n - 1 else ACT_NONE
-            yout = acts[i + 1] if i < n - 1 else acts[i]
-            # fwd args: (x, n_layers, k, ws_bf16T, *W, *b) -> W[i] at 4+i
-            if ctx.needs_input_grad[4 + i]:
-                dwT, db = ext.linear_bwd_dwdb_bf16(dy, acts[i], yout, act, k)
-                dws[i] = dwT.permute(0, 2, 1)     # -> (k, in, out)
-                dbs[i] = db.view(k, 1, -1)
+            yout = acts[i + 1] if i < n - 1 else acts[i]  # dummy when act=0
+            if need_w[i]:
+                dw, db = ext.linear_bwd_dwdb_bf16(dy, acts[i], yout, act, G)
+                if ctx.transposed:
+                    dw, db = dw.permute(0, 2, 1), db.view(G, 1, -1)
+                dws[i], dbs[i] = dw, db
             if i > 0:
-                dy = ext.linear_bwd_dx_bf16(dy, ws[i], yout, act, k, 0)
-        return (None, None, None, None, *dws, *dbs)
+                dy = ext.linear_bwd_dx_bf16(dy, ws[i], yout, act, G, 0)
+            elif ctx.needs_input_grad[0]:
+                dx = ext.linear_bwd_dx_bf16(dy, ws[0], yout, act, G,
+                                            1).to(torch.float32)
+        return (dx, None, None, None, None, None, *dws, *dbs)
+
+
+def mlp_forward_bf16(x, ws_f32, bs_f32, ws_bf16, grad_row_start: int = 0):
+    return _MLPBF16.apply(x, len(ws_f32), 1, grad_row_start, False,
+                          tuple(ws_bf16), *ws_f32, *bs_f32)
+
+
+def twin_mlp_forward_bf16(x, stacked_ws_f32, stacked_bs_f32, ws_bf16):
+    return _MLPBF16.apply(x, len(ws_bf16), 2, 0, False, tuple(ws_bf16),
+                          *stacked_ws_f32, *stacked_bs_f32)
 
 
 def grouped_mlp_bf16(x, W_f32_list, b_f32_list, ws_bf16T_list, k: int):
-    return _GroupedMLPBF16.apply(x, len(W_f32_list), k,
-                                 tuple(ws_bf16T_list), *W_f32_list,
-                                 *b_f32_list)
+    """CARE mixture-of-k-encoders as grouped bf16 GEMMs: [k,B,out] fp32."""
+    return _MLPBF16.apply(x, len(W_f32_list), k, 0, True,
+                          tuple(ws_bf16T_list), *W_f32_list, *b_f32_list)

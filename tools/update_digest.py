@@ -1,14 +1,22 @@
-"""Bit-exact digest of the bf16 manual update, for before/after
-comparison of a change that must not alter results.
+"""Bit-exact digest of the bf16 manual update and of the autograd
+updates, for before/after comparison of a change that must not alter
+results.
 
 For each engine config x DSAC_FUSE_TAIL in {1, 0}: 6 update_tensors
 calls (counter RNG on) over three fixed batches, then the SHA-256 of
 every flat parameter group and of the six metric dicts.  Then the same
 with prioritized batches, with a forced world-1 data-parallel group
-attached, and with that group through capture_dp / dp_graphed_update.  Uses the
-engines' public API only, so the same file runs on any commit:
+attached, and with that group through capture_dp / dp_graphed_update.
+
+The autograd updates (ops/functional.py's MLP Functions) the same way: fp32
+under the four settings of DSAC_F32_CHAIN x DSAC_F32_CHAIN_BWD, and bf16
+with DSAC_NO_MANUAL=1.
+
+Uses the engines' public API only, so the same file runs on any commit:
 
     python tools/update_digest.py > digest.txt     # on both commits
+    python tools/update_digest.py autograd         # that section alone
+                                                   # (or: manual)
 """
 
 import hashlib
@@ -48,14 +56,15 @@ def fill_replay(cfg):
     return replay
 
 
-def run(name, make_cfg, engine_cls, fuse, per=False, ddp=None, graphs=False):
+def run(name, make_cfg, engine_cls, fuse, per=False, ddp=None, graphs=False,
+        precision="bf16"):
     """per: the batches carry IS weights and indices (no replay attached).
     ddp: a data-parallel group to attach.  graphs: capture_dp, then
     dp_graphed_update instead of update_tensors."""
     os.environ["DSAC_FUSE_TAIL"] = fuse
     torch.manual_seed(0)
     cfg = make_cfg()
-    e = engine_cls(cfg, "cuda:0", precision="bf16")
+    e = engine_cls(cfg, "cuda:0", precision=precision)
     if ddp is not None:
         e.attach_ddp(ddp)
     B = cfg.batch_size
@@ -91,18 +100,30 @@ def run(name, make_cfg, engine_cls, fuse, per=False, ddp=None, graphs=False):
     assert all(torch.isfinite(x).all() for x in metrics), tag
 
 
-def main():
+def run_autograd(cases):
+    """The updates that differentiate through ops/functional.py."""
+    def with_env(env, name, make_cfg, cls, precision):
+        os.environ.update(env)
+        try:
+            tag = " ".join(f"{k[5:].lower()}={v}" for k, v in env.items())
+            run(f"{name} {precision} {tag}", make_cfg, cls, "1",
+                precision=precision)
+        finally:
+            for k in env:
+                del os.environ[k]
+
+    for case in cases:
+        for fwd in ("0", "1"):
+            for bwd in ("0", "1"):
+                with_env({"DSAC_F32_CHAIN": fwd, "DSAC_F32_CHAIN_BWD": bwd},
+                         *case, "fp32")
+        with_env({"DSAC_NO_MANUAL": "1"}, *case, "bf16")
+
+
+def run_manual(cases):
+    """The bf16 manual update (see the module docstring)."""
     import torch.distributed as dist
     from distributed_sac_amd.parallel import DataParallelGroup
-    tmp = tempfile.mkdtemp()
-    cases = [
-        ("sac_small", lambda: small_cfg("sac"), SACEngine),
-        ("mtsac_small", lambda: small_cfg("mtsac"), SACEngine),
-        ("mtsac_shipped", lambda: load_variant("mtsac"), SACEngine),
-        ("care_modified", lambda: care_cfg(tmp, modified=True), CAREEngine),
-        ("care_original",
-         lambda: care_cfg(tmp, modified=False, num_tasks=1), CAREEngine),
-    ]
     for name, make_cfg, cls in cases:
         for fuse in ("1", "0"):
             run(name, make_cfg, cls, fuse)
@@ -120,6 +141,23 @@ def main():
     finally:
         if dist.is_initialized():
             dist.destroy_process_group()
+
+
+def main():
+    tmp = tempfile.mkdtemp()
+    cases = [
+        ("sac_small", lambda: small_cfg("sac"), SACEngine),
+        ("mtsac_small", lambda: small_cfg("mtsac"), SACEngine),
+        ("mtsac_shipped", lambda: load_variant("mtsac"), SACEngine),
+        ("care_modified", lambda: care_cfg(tmp, modified=True), CAREEngine),
+        ("care_original",
+         lambda: care_cfg(tmp, modified=False, num_tasks=1), CAREEngine),
+    ]
+    sections = sys.argv[1:] or ["manual", "autograd"]
+    if "manual" in sections:
+        run_manual(cases)
+    if "autograd" in sections:
+        run_autograd([cases[0], cases[1], cases[3], cases[4]])
 
 
 if __name__ == "__main__":
