@@ -26,6 +26,15 @@
 // 16-lane b128 read groups touch all 64 banks exactly once —
 // conflict-free without padding tricks (see cdna_hip_programming.md §2).
 //
+// The shipped single-launch kernels (k_bf16_chain_fwd_pipe /
+// k_bf16_chain_dx_pipe, selector pipe=1) re-shape the packed k-loop: 1024
+// threads = 16 waves, PAIRS of column tiles per wave (a 400-wide layer's
+// 25 tiles keep 13 of 16 waves busy, half the dependent k-steps' loads
+// per wave) and a branch-free pipeline 4 k-steps deep (8 KiB in flight
+// per wave, 16 waves).  Same accumulators, same k order, same bits; see
+// packed_kloop and profiles/chain_pipe.md.  The 8-wave quad kernels stay
+// as pipe=0 (DSAC_CHAIN_PIPE=0), for raw weights, RM=2 and the pair launch.
+//
 // grid (ceil(M/TM), 1, G).  G>1 = twin critics: shared x, per-group
 // weights/biases/outputs (same convention as k_bf16_fwd).
 
@@ -48,7 +57,7 @@ static constexpr int CMAX = 768;  // max layer width / input width
 static constexpr int CPAD = 776;  // LDS row stride (u16): 388 dwords ≡ 4 mod 64
                                   // -> 16-lane b128 A-fragment groups hit
                                   // all 64 banks exactly once
-static constexpr int NTHR = 512;  // 8 waves
+static constexpr int NTHR = 512;  // 8 waves: the parent mapping's block
 
 #define CHAIN_CHECK_BF16(t) \
   TORCH_CHECK((t).is_cuda() && (t).scalar_type() == torch::kBFloat16, \
@@ -94,19 +103,97 @@ __device__ __forceinline__ bf16x8 load_bfrag(const u16* __restrict__ w,
   return bf16x8{};
 }
 
+// k-loop of the FRAGMENT-PACKED path, shared by the forward and the dx
+// body: a rotating software pipeline over DEPTH + 1 fragment sets of TQ
+// tiles.  The loads of k-step ks + DEPTH are issued before the MFMAs of
+// k-step ks, so DEPTH * TQ 1-KiB loads are in flight per wave.  bp[j] is
+// the lane's element offset of tile j's k-step 0; one k-step is 512 u16.
+// Correct for every KS >= 1, shorter than DEPTH included: no load reaches
+// past step KS - 1, and mf(set, k) runs once per step in ascending order,
+// so each accumulator sums exactly as with any other DEPTH.
+//
+// DEPTH == 2 is the 8-wave quad kernels' ladder, kept as it was: its
+// look-ahead loads sit under (uniform) branches, and the compiler's
+// wait-count merge over those branches drains all loads at the loop head,
+// once per three k-steps.  Every other DEPTH runs branch-free: a
+// look-ahead past the last step re-reads step KS - 1 (a cache hit nobody
+// consumes, DEPTH - KS % (DEPTH + 1) of them per pass) so the waits inside
+// the loop leave DEPTH * TQ loads outstanding.  The pair launch, two
+// workgroups per CU, measured 0.8 us slower with those extra loads and
+// stays on the ladder.
+template <int TQ, int DEPTH, class MF>
+__device__ __forceinline__ void packed_kloop(const u16* __restrict__ wpl,
+                                             const long (&bp)[TQ], int KS,
+                                             MF mf) {
+  constexpr int NS = DEPTH + 1;
+  bf16x8 S[NS][TQ];
+#define LOADP(set, ks_)                                                   \
+  _Pragma("unroll") for (int j = 0; j < TQ; ++j)                          \
+    S[set][j] = *(const bf16x8*)&wpl[bp[j] + (long)(ks_) * 512];
+  if constexpr (DEPTH == 2) {
+    LOADP(0, 0)
+    if (1 < KS) LOADP(1, 1)
+    int ks = 0;
+    while (ks + 3 <= KS) {
+      LOADP(2, ks + 2)
+      mf(S[0], ks * 32);
+      if (ks + 3 < KS) {
+        LOADP(0, ks + 3)
+      }
+      mf(S[1], (ks + 1) * 32);
+      if (ks + 4 < KS) {
+        LOADP(1, ks + 4)
+      }
+      mf(S[2], (ks + 2) * 32);
+      ks += 3;
+    }
+    if (KS - ks == 1) {
+      mf(S[0], ks * 32);
+    } else if (KS - ks == 2) {
+      mf(S[0], ks * 32);
+      mf(S[1], (ks + 1) * 32);
+    }
+  } else {
+    const int last = KS - 1;
+#define LOADC(set, ks_) LOADP(set, (ks_) < last ? (ks_) : last)
+#pragma unroll
+    for (int s = 0; s < DEPTH; ++s) LOADC(s, s)
+    int ks = 0;
+    for (; ks + NS <= KS; ks += NS) {
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        // refill the set the previous step consumed
+        LOADC((s + DEPTH) % NS, ks + s + DEPTH)
+        mf(S[s], (ks + s) * 32);
+      }
+    }
+    // the last KS % NS steps sit in sets 0 .. KS % NS - 1
+#pragma unroll
+    for (int s = 0; s < DEPTH; ++s)
+      if (ks + s < KS) mf(S[s], (ks + s) * 32);
+#undef LOADC
+  }
+#undef LOADP
+}
+
 // The whole forward chain of ONE (row tile, group) workgroup; shared by
 // the single launch and the pair launch below.  PACKED_ONLY compiles the
 // k-loop down to the fragment-packed loader (every d.wp[li] must be set):
 // without the two raw-weight loaders the RM=1 body fits 128 VGPRs, i.e.
-// two workgroups per CU.
-template <int RM, bool PACKED_ONLY>
+// two workgroups per CU.  WAVES / TQ / DEPTH (waves per workgroup,
+// column tiles per wave per pass, k-steps of look-ahead) re-shape the
+// packed k-loop only: the raw-weight loaders keep the 8-wave quad mapping.
+template <int RM, bool PACKED_ONLY, int WAVES = 8, int TQ = 4, int DEPTH = 2>
 __device__ __forceinline__ void chain_fwd_body(
     const void* __restrict__ x1, const void* __restrict__ x2,
     int C1, int C2, int x1f, int x2f, int rowcat, int M1,
     u16* __restrict__ xsave,
     const ChainFwdDesc& d, void* __restrict__ y, int M, int out_f32,
     int tile, int g) {
+  static_assert(PACKED_ONLY || (WAVES == 8 && TQ == 4 && DEPTH == 2),
+                "the raw-weight loaders are written for the 8-wave quad");
   constexpr int TMv = 16 * RM;
+  constexpr int NT = WAVES * 64;   // threads per workgroup
   __shared__ u16 sa[2][TMv][CPAD];
   const int m0 = tile * TMv;
   const int tid = threadIdx.x;
@@ -118,7 +205,7 @@ __device__ __forceinline__ void chain_fwd_body(
   // zero both activation buffers (pads must read 0 in the MFMA A-frags)
   {
     unsigned* p = (unsigned*)sa;
-    for (int i = tid; i < 2 * TMv * CPAD / 2; i += NTHR) p[i] = 0u;
+    for (int i = tid; i < 2 * TMv * CPAD / 2; i += NT) p[i] = 0u;
   }
   __syncthreads();
 
@@ -128,7 +215,7 @@ __device__ __forceinline__ void chain_fwd_body(
   {
     const int r = tid >> 5;      // 32 threads per row covers 16 rows/pass
     const int lc = tid & 31;
-    for (int rr = r; rr < rowlim; rr += NTHR / 32) {
+    for (int rr = r; rr < rowlim; rr += NT / 32) {
       const long row = m0 + rr;
       for (int c = lc; c < K0; c += 32) {
         float v;
@@ -155,10 +242,10 @@ __device__ __forceinline__ void chain_fwd_body(
   if (xsave != nullptr && g == 0) {
     const int r = tid >> 5;
     const int lc = tid & 31;
-    for (int rr = r; rr < rowlim; rr += NTHR / 32) {
+    for (int rr = r; rr < rowlim; rr += NT / 32) {
       u16* dst = xsave + (long)(m0 + rr) * K0;
       const u16* src = &sa[0][rr][0];
-      for (int c = lc * 8; c + 8 <= K0; c += (NTHR / 32) * 8)
+      for (int c = lc * 8; c + 8 <= K0; c += (NT / 32) * 8)
         *(uint4*)&dst[c] = *(const uint4*)&src[c];
     }
     if ((K0 & 7) && tid < TMv && tid < rowlim) {
@@ -189,13 +276,13 @@ __device__ __forceinline__ void chain_fwd_body(
     const bool k_aligned = (K % 8) == 0;
     const int kbody = k_aligned ? (K & ~31) : 0;
 
-    for (int t0 = wid * 4; t0 < ntiles; t0 += 4 * (NTHR / 64)) {
-      const int nq = (ntiles - t0 < 4) ? (ntiles - t0) : 4;
-      f32x4 acc[RM][4];
+    for (int t0 = wid * TQ; t0 < ntiles; t0 += TQ * WAVES) {
+      const int nq = (ntiles - t0 < TQ) ? (ntiles - t0) : TQ;
+      f32x4 acc[RM][TQ];
 #pragma unroll
       for (int m = 0; m < RM; ++m)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[m][j] = f32x4{};
+        for (int j = 0; j < TQ; ++j) acc[m][j] = f32x4{};
       // Per-lane CLAMPED row bases: surplus quad slots (j >= nq) and
       // out-of-range rows of a partial-N tile load a VALID row instead
       // of branching — their MFMA lanes produce garbage that the
@@ -206,23 +293,23 @@ __device__ __forceinline__ void chain_fwd_body(
       // path — the guarded loop (a per-load branch + vmcnt drain) made
       // one straggler wave serialize the whole chain at the layer
       // barrier.
-      long rb[4];
+      long rb[TQ];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
+      for (int j = 0; j < TQ; ++j) {
         int row = (t0 + (j < nq ? j : nq - 1)) * 16 + fi;
         if (row >= N) row = N - 1;
         rb[j] = (long)row * K;
       }
 
 #define LOADQ(dst, kk)                                                    \
-      _Pragma("unroll") for (int j = 0; j < 4; ++j)                       \
+      _Pragma("unroll") for (int j = 0; j < TQ; ++j)                      \
         dst[j] = *(const bf16x8*)&wg[rb[j] + fk * 8 + (kk)];
 #define MF4(bset, kk)                                                     \
       {                                                                   \
         _Pragma("unroll") for (int m = 0; m < RM; ++m) {                  \
           const bf16x8 a_ =                                               \
               *(const bf16x8*)&sa[cur][m * 16 + fi][(kk) + fk * 8];       \
-          _Pragma("unroll") for (int j = 0; j < 4; ++j)                   \
+          _Pragma("unroll") for (int j = 0; j < TQ; ++j)                  \
             acc[m][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(          \
                 a_, bset[j], acc[m][j], 0, 0, 0);                         \
         }                                                                 \
@@ -235,55 +322,25 @@ __device__ __forceinline__ void chain_fwd_body(
         // K and partial-N tiles uniformly).
         const int KS = (K + 31) >> 5;
         const int NTp = (N + 15) >> 4;
-        const u16* wpl = d.wp[li];
-        long bp[4];
+        long bp[TQ];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
+        for (int j = 0; j < TQ; ++j) {
           int tt = t0 + (j < (nq > 0 ? nq : 1) ? j
                          : (nq > 0 ? nq - 1 : 0));
           if (tt >= NTp) tt = NTp - 1;
           if (tt < 0) tt = 0;
           bp[j] = (((long)g * NTp + tt) * KS) * 512 + lane * 8;
         }
-#define LOADP(dst, kk)                                                    \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j)                     \
-          dst[j] = *(const bf16x8*)&wpl[bp[j] + (long)(kk) * 16];
-        // (kk is the k element offset; one 32-k step = 512 u16 = kk*16
-        //  since kk advances by 32)
-        {
-          bf16x8 S0[4], S1[4], S2[4];
-          const int pbody = KS * 32;
-          LOADP(S0, 0)
-          if (32 < pbody) LOADP(S1, 32)
-          int k = 0;
-          while (k + 96 <= pbody) {
-            LOADP(S2, k + 64)
-            MF4(S0, k)
-            if (k + 96 < pbody) {
-              LOADP(S0, k + 96)
-            }
-            MF4(S1, k + 32)
-            if (k + 128 < pbody) {
-              LOADP(S1, k + 128)
-            }
-            MF4(S2, k + 64)
-            k += 96;
-          }
-          if (pbody - k == 32) {
-            MF4(S0, k)
-          } else if (pbody - k == 64) {
-            MF4(S0, k)
-            MF4(S1, k + 32)
-          }
-        }
-#undef LOADP
+        packed_kloop<TQ, DEPTH>(
+            d.wp[li], bp, KS,
+            [&](const bf16x8 (&bset)[TQ], int kk) { MF4(bset, kk) });
       } else if (k_aligned) {
         // unconditional loads, 3-set rotating software pipeline: loads
         // run TWO k-steps ahead of their MFMAs (12 B-fragments in
         // flight), hiding cold-L2/L3 weight-miss latency that a 1-deep
         // pipeline left exposed.
         if (kbody >= 32) {
-          bf16x8 S0[4], S1[4], S2[4];
+          bf16x8 S0[TQ], S1[TQ], S2[TQ];
           LOADQ(S0, 0)
           if (32 < kbody) LOADQ(S1, 32)
           int k = 0;
@@ -313,9 +370,9 @@ __device__ __forceinline__ void chain_fwd_body(
           // multiply the zero LDS pad.
           const int k8 = kbody + fk * 8;
           const int k8c = (k8 + 8 <= K) ? k8 : (K - 8);
-          bf16x8 B[4];
+          bf16x8 B[TQ];
 #pragma unroll
-          for (int j = 0; j < 4; ++j)
+          for (int j = 0; j < TQ; ++j)
             B[j] = *(const bf16x8*)&wg[rb[j] + k8c];
           MF4(B, kbody)
         }
@@ -323,9 +380,9 @@ __device__ __forceinline__ void chain_fwd_body(
         // odd-K layer (the 49/53-d layer-0 inputs): guarded loads
         for (int k = 0; k < K; k += 32) {
           const int k8 = k + fk * 8;
-          bf16x8 B[4];
+          bf16x8 B[TQ];
 #pragma unroll
-          for (int j = 0; j < 4; ++j)
+          for (int j = 0; j < TQ; ++j)
             B[j] = (j < nq) ? load_bfrag(wg, t0 * 16 + j * 16 + fi, N, K, k8)
                             : bf16x8{};
           MF4(B, k)
@@ -338,7 +395,7 @@ __device__ __forceinline__ void chain_fwd_body(
 #pragma unroll
       for (int m = 0; m < RM; ++m) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
+        for (int q = 0; q < TQ; ++q) {
           if (q >= nq) break;
           const f32x4 a = acc[m][q];
           const int col = (t0 + q) * 16 + fi;
@@ -368,7 +425,7 @@ __device__ __forceinline__ void chain_fwd_body(
     if (!last) {
       // zero the stale tail of the next buffer: cols [N, prevw(nb))
       const int pw = nb ? prevw1 : prevw0;
-      for (int i = tid; i < TMv * (pw > N ? pw - N : 0); i += NTHR) {
+      for (int i = tid; i < TMv * (pw > N ? pw - N : 0); i += NT) {
         const int r = i / (pw - N), c = N + i % (pw - N);
         sa[nb][r][c] = 0;
       }
@@ -379,10 +436,10 @@ __device__ __forceinline__ void chain_fwd_body(
       if (ag != nullptr) {
         const int r2 = tid >> 5;
         const int lc2 = tid & 31;
-        for (int rr = r2; rr < rowlim; rr += NTHR / 32) {
+        for (int rr = r2; rr < rowlim; rr += NT / 32) {
           u16* dst = ag + (long)(m0 + rr) * N;
           const u16* src = &sa[nb][rr][0];
-          for (int c = lc2 * 8; c + 8 <= N; c += (NTHR / 32) * 8)
+          for (int c = lc2 * 8; c + 8 <= N; c += (NT / 32) * 8)
             *(uint4*)&dst[c] = *(const uint4*)&src[c];
         }
         if ((N & 7) && tid < TMv && tid < rowlim) {
@@ -404,6 +461,19 @@ __global__ __launch_bounds__(NTHR) void k_bf16_chain_fwd(
     ChainFwdDesc d, void* __restrict__ y, int M, int out_f32) {
   chain_fwd_body<RM, false>(x1, x2, C1, C2, x1f, x2f, rowcat, M1, xsave, d,
                             y, M, out_f32, blockIdx.x, blockIdx.z);
+}
+
+// The single launch with the re-shaped packed k-loop (every layer packed,
+// 16-row tiles).
+template <int WAVES, int TQ, int DEPTH>
+__global__ __launch_bounds__(WAVES * 64) void k_bf16_chain_fwd_pipe(
+    const void* __restrict__ x1, const void* __restrict__ x2,
+    int C1, int C2, int x1f, int x2f, int rowcat, int M1,
+    u16* __restrict__ xsave,
+    ChainFwdDesc d, void* __restrict__ y, int M, int out_f32) {
+  chain_fwd_body<1, true, WAVES, TQ, DEPTH>(
+      x1, x2, C1, C2, x1f, x2f, rowcat, M1, xsave, d, y, M, out_f32,
+      blockIdx.x, blockIdx.z);
 }
 
 // ---------------------------------------------------------------------------
@@ -672,10 +742,16 @@ struct ChainDxDesc {
   int dx0_lo;           // -1 = no input gradient
 };
 
-__global__ __launch_bounds__(NTHR) void k_bf16_chain_dx(
-    const u16* __restrict__ dy_last, ChainDxDesc d,
+// PACKED_ONLY / WAVES / TQ / DEPTH as in chain_fwd_body: every layer the
+// walk crosses must then have its d.wp set.
+template <bool PACKED_ONLY, int WAVES = 8, int TQ = 4, int DEPTH = 2>
+__device__ __forceinline__ void chain_dx_body(
+    const u16* __restrict__ dy_last, const ChainDxDesc& d,
     float* __restrict__ dx0, int M) {
+  static_assert(PACKED_ONLY || (WAVES == 8 && TQ == 4 && DEPTH == 2),
+                "the raw-weight loaders are written for the 8-wave quad");
   constexpr int TMv = 16;
+  constexpr int NT = WAVES * 64;   // threads per workgroup
   __shared__ u16 sd[2][TMv][CPAD];
   const int g = blockIdx.z;
   const int m0 = blockIdx.x * TMv;
@@ -686,7 +762,7 @@ __global__ __launch_bounds__(NTHR) void k_bf16_chain_dx(
 
   {
     unsigned* p = (unsigned*)sd;
-    for (int i = tid; i < 2 * TMv * CPAD / 2; i += NTHR) p[i] = 0u;
+    for (int i = tid; i < 2 * TMv * CPAD / 2; i += NT) p[i] = 0u;
   }
   __syncthreads();
 
@@ -696,7 +772,7 @@ __global__ __launch_bounds__(NTHR) void k_bf16_chain_dx(
     const int r = tid >> 5;
     const int lc = tid & 31;
     const u16* src = dy_last + (long)g * M * NL;
-    for (int rr = r; rr < rowlim; rr += NTHR / 32)
+    for (int rr = r; rr < rowlim; rr += NT / 32)
       for (int c = lc; c < NL; c += 32)
         sd[0][rr][c] = src[(long)(m0 + rr) * NL + c];
   }
@@ -718,7 +794,7 @@ __global__ __launch_bounds__(NTHR) void k_bf16_chain_dx(
           ? d.yout[li] + (long)g * d.yo_gs[li] : nullptr;
       u16* sv = d.dysave[li] != nullptr
           ? d.dysave[li] + (long)g * M * N : nullptr;
-      for (int rr = r; rr < rowlim; rr += NTHR / 32) {
+      for (int rr = r; rr < rowlim; rr += NT / 32) {
         const long row = m0 + rr;
         for (int c = lc; c < N; c += 32) {
           u16 v = sd[cur][rr][c];
@@ -750,78 +826,50 @@ __global__ __launch_bounds__(NTHR) void k_bf16_chain_dx(
     float* dx0g = want_dx0
         ? dx0 + (long)g * M * (K - col_lo) : nullptr;
 
-    for (int t0 = t_lo + wid * 4; t0 < ntiles; t0 += 4 * (NTHR / 64)) {
-      const int nq = (ntiles - t0 < 4) ? (ntiles - t0) : 4;
-      f32x4 acc[1][4];
+    for (int t0 = t_lo + wid * TQ; t0 < ntiles; t0 += TQ * WAVES) {
+      const int nq = (ntiles - t0 < TQ) ? (ntiles - t0) : TQ;
+      f32x4 acc[1][TQ];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) acc[0][j] = f32x4{};
-      long rb[4];
+      for (int j = 0; j < TQ; ++j) acc[0][j] = f32x4{};
+      long rb[TQ];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
+      for (int j = 0; j < TQ; ++j) {
         int row = (t0 + (j < nq ? j : nq - 1)) * 16 + fi;   // k index
         if (row >= K) row = K - 1;
         rb[j] = (long)row * N;
       }
 
 #define LOADQ(dst, kk)                                                    \
-      _Pragma("unroll") for (int j = 0; j < 4; ++j)                       \
+      _Pragma("unroll") for (int j = 0; j < TQ; ++j)                      \
         dst[j] = *(const bf16x8*)&wtg[rb[j] + fk * 8 + (kk)];
 #define MF4(bset, kk)                                                     \
       {                                                                   \
         const bf16x8 a_ =                                                 \
             *(const bf16x8*)&sd[cur][fi][(kk) + fk * 8];                  \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j)                     \
+        _Pragma("unroll") for (int j = 0; j < TQ; ++j)                    \
           acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(            \
               a_, bset[j], acc[0][j], 0, 0, 0);                           \
       }
 
-      if (d.wp[li] != nullptr) {
+      if (PACKED_ONLY || d.wp[li] != nullptr) {
         // fragment-packed W^T: unit-stride loads, guards baked in
         const int KSp = (N + 31) >> 5;
         const int NTp = (K + 15) >> 4;
-        const u16* wpl = d.wp[li];
-        long bp[4];
+        long bp[TQ];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
+        for (int j = 0; j < TQ; ++j) {
           int tt = t0 + (j < (nq > 0 ? nq : 1) ? j
                          : (nq > 0 ? nq - 1 : 0));
           if (tt >= NTp) tt = NTp - 1;
           if (tt < 0) tt = 0;
           bp[j] = (((long)g * NTp + tt) * KSp) * 512 + lane * 8;
         }
-#define LOADP(dst, kk)                                                    \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j)                     \
-          dst[j] = *(const bf16x8*)&wpl[bp[j] + (long)(kk) * 16];
-        {
-          bf16x8 S0[4], S1[4], S2[4];
-          const int pbody = KSp * 32;
-          LOADP(S0, 0)
-          if (32 < pbody) LOADP(S1, 32)
-          int k = 0;
-          while (k + 96 <= pbody) {
-            LOADP(S2, k + 64)
-            MF4(S0, k)
-            if (k + 96 < pbody) {
-              LOADP(S0, k + 96)
-            }
-            MF4(S1, k + 32)
-            if (k + 128 < pbody) {
-              LOADP(S1, k + 128)
-            }
-            MF4(S2, k + 64)
-            k += 96;
-          }
-          if (pbody - k == 32) {
-            MF4(S0, k)
-          } else if (pbody - k == 64) {
-            MF4(S0, k)
-            MF4(S1, k + 32)
-          }
-        }
-#undef LOADP
+        packed_kloop<TQ, DEPTH>(
+            d.wp[li], bp, KSp,
+            [&](const bf16x8 (&bset)[TQ], int kk) { MF4(bset, kk) });
       } else if (n_aligned) {
         if (nbody >= 32) {
-          bf16x8 S0[4], S1[4], S2[4];
+          bf16x8 S0[TQ], S1[TQ], S2[TQ];
           LOADQ(S0, 0)
           if (32 < nbody) LOADQ(S1, 32)
           int k = 0;
@@ -848,9 +896,9 @@ __global__ __launch_bounds__(NTHR) void k_bf16_chain_dx(
         if (nbody < N) {
           const int k8 = nbody + fk * 8;
           const int k8c = (k8 + 8 <= N) ? k8 : (N - 8);
-          bf16x8 B[4];
+          bf16x8 B[TQ];
 #pragma unroll
-          for (int j = 0; j < 4; ++j)
+          for (int j = 0; j < TQ; ++j)
             B[j] = *(const bf16x8*)&wtg[rb[j] + k8c];
           MF4(B, nbody)
         }
@@ -858,9 +906,9 @@ __global__ __launch_bounds__(NTHR) void k_bf16_chain_dx(
         // tiny-N head layers (N = 1 or 8): guarded single pass
         for (int k = 0; k < N; k += 32) {
           const int k8 = k + fk * 8;
-          bf16x8 B[4];
+          bf16x8 B[TQ];
 #pragma unroll
-          for (int j = 0; j < 4; ++j)
+          for (int j = 0; j < TQ; ++j)
             B[j] = (j < nq)
                 ? load_bfrag(wtg, t0 * 16 + j * 16 + fi, K, N, k8)
                 : bf16x8{};
@@ -873,7 +921,7 @@ __global__ __launch_bounds__(NTHR) void k_bf16_chain_dx(
       // epilogue: when producing dy_{li-1}, apply ITS relu' mask here
       // (its dysave is written by the coalesced copy after the barrier)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
+      for (int q = 0; q < TQ; ++q) {
         if (q >= nq) break;
         const f32x4 a = acc[0][q];
         const int col = (t0 + q) * 16 + fi;   // k index
@@ -899,7 +947,7 @@ __global__ __launch_bounds__(NTHR) void k_bf16_chain_dx(
     if (want_dx0) break;
     {
       const int pw = nb ? prevw1 : prevw0;
-      for (int i = tid; i < TMv * (pw > K ? pw - K : 0); i += NTHR) {
+      for (int i = tid; i < TMv * (pw > K ? pw - K : 0); i += NT) {
         const int r = i / (pw - K), c = K + i % (pw - K);
         sd[nb][r][c] = 0;
       }
@@ -910,10 +958,10 @@ __global__ __launch_bounds__(NTHR) void k_bf16_chain_dx(
     if (sv_n != nullptr) {
       const int r2 = tid >> 5;
       const int lc2 = tid & 31;
-      for (int rr = r2; rr < rowlim; rr += NTHR / 32) {
+      for (int rr = r2; rr < rowlim; rr += NT / 32) {
         u16* dst = sv_n + (long)(m0 + rr) * K;
         const u16* src = &sd[nb][rr][0];
-        for (int c = lc2 * 8; c + 8 <= K; c += (NTHR / 32) * 8)
+        for (int c = lc2 * 8; c + 8 <= K; c += (NT / 32) * 8)
           *(uint4*)&dst[c] = *(const uint4*)&src[c];
       }
       if ((K & 7) && tid < TMv && tid < rowlim) {
@@ -925,19 +973,36 @@ __global__ __launch_bounds__(NTHR) void k_bf16_chain_dx(
   }
 }
 
+__global__ __launch_bounds__(NTHR) void k_bf16_chain_dx(
+    const u16* __restrict__ dy_last, ChainDxDesc d,
+    float* __restrict__ dx0, int M) {
+  chain_dx_body<false>(dy_last, d, dx0, M);
+}
+
+template <int WAVES, int TQ, int DEPTH>
+__global__ __launch_bounds__(WAVES * 64) void k_bf16_chain_dx_pipe(
+    const u16* __restrict__ dy_last, ChainDxDesc d,
+    float* __restrict__ dx0, int M) {
+  chain_dx_body<true, WAVES, TQ, DEPTH>(dy_last, d, dx0, M);
+}
+
 // Host binding: [dy_0 .. dy_{L-1} [, dx0]] = mlp_chain_dx_bf16(
-//     dy_last, wts, youts, K0, acts_flags, G, save_dys, dx0_lo)
+//     dy_last, wts, youts, K0, acts_flags, G, save_dys, dx0_lo, wps=[],
+//     pipe=0)
 // wts[i]: TRANSPOSED bf16 weights [G*K_i, N_i]; youts[i]: mask tensors
 // (post-act outputs, same [G?,M,N_i] layout) or an empty tensor where
 // act=0.  Returns the per-layer MASKED dy tensors (empty placeholders
 // when save_dys=0) and, when dx0_lo >= 0, the fp32 input gradient
 // restricted to columns >= dx0_lo, per group [G, M, K0-dx0_lo].
+// pipe: 0 = the 8-wave quad kernel, 1 = k_bf16_chain_dx_pipe (needs a
+// packed buffer for every layer the walk crosses).
 static std::vector<torch::Tensor> mlp_chain_dx_bf16(
     torch::Tensor dy_last, std::vector<torch::Tensor> wts,
     std::vector<torch::Tensor> youts, long K0,
     std::vector<long> acts, long G, long save_dys, long dx0_lo,
-    std::vector<torch::Tensor> wps) {
+    std::vector<torch::Tensor> wps, long pipe) {
   CHAIN_CHECK_BF16(dy_last);
+  TORCH_CHECK(pipe >= 0 && pipe <= 1, "chain dx: no kernel for pipe=", pipe);
   const int L = (int)wts.size();
   TORCH_CHECK(L >= 1 && L <= 6 && (int)youts.size() == L
               && (int)acts.size() == L);
@@ -968,6 +1033,8 @@ static std::vector<torch::Tensor> mlp_chain_dx_bf16(
       d.wp[i] = (const u16*)wps[i].data_ptr();
       keep.push_back(wps[i]);
     }
+    TORCH_CHECK(pipe == 0 || d.wp[i] != nullptr || (i == 0 && dx0_lo < 0),
+                "chain dx pipe: no packed weights for layer ", i);
     d.N[i] = (int)N;
     d.act[i] = (int)acts[i];
     d.yout[i] = nullptr;
@@ -999,24 +1066,31 @@ static std::vector<torch::Tensor> mlp_chain_dx_bf16(
     out.push_back(dx0);
   }
   dim3 grid((M + 15) / 16, 1, G);
-  hipLaunchKernelGGL(k_bf16_chain_dx, grid, dim3(NTHR), 0, cur_stream3(),
-                     (const u16*)dyc.data_ptr(), d,
-                     dx0_lo >= 0 ? dx0.data_ptr<float>() : nullptr,
-                     (int)M);
+#define CHAIN_DX_LAUNCH(kern, nthr)                                       \
+  hipLaunchKernelGGL(kern, grid, dim3(nthr), 0, cur_stream3(),            \
+                     (const u16*)dyc.data_ptr(), d,                       \
+                     dx0_lo >= 0 ? dx0.data_ptr<float>() : nullptr,       \
+                     (int)M)
+  if (pipe == 1)
+    CHAIN_DX_LAUNCH((k_bf16_chain_dx_pipe<16, 2, 4>), 1024);
+  else
+    CHAIN_DX_LAUNCH(k_bf16_chain_dx, NTHR);
+#undef CHAIN_DX_LAUNCH
   return out;
 }
 
 // Checks one forward chain's arguments, allocates its outputs into `out`
-// (the binding's return format) and fills the kernel-side job.  `pair`:
-// the pair launch's two differences — a packed buffer is REQUIRED for
-// every layer, and a save_acts=0 job gets no bf16 input copy (out[1] is
-// an empty tensor; nobody reads a no-grad forward's saved input).
+// (the binding's return format) and fills the kernel-side job.
+// `need_packed`: a packed buffer is REQUIRED for every layer (PACKED_ONLY
+// kernels).  `pair`: a save_acts=0 job of the pair launch gets no bf16
+// input copy (out[1] is an empty tensor; nobody reads a no-grad forward's
+// saved input).
 static ChainFwdJob make_fwd_job(
     torch::Tensor x1, torch::Tensor x2,
     const std::vector<torch::Tensor>& ws,
     const std::vector<torch::Tensor>& bs, long act_last, long G,
     long out_f32, long rowcat, long save_acts,
-    const std::vector<torch::Tensor>& wps, bool pair,
+    const std::vector<torch::Tensor>& wps, bool need_packed, bool pair,
     std::vector<torch::Tensor>& keep, std::vector<torch::Tensor>& out) {
   const int L = (int)ws.size();
   TORCH_CHECK(L >= 1 && L <= 6 && (int)bs.size() == L);
@@ -1047,8 +1121,8 @@ static ChainFwdJob make_fwd_job(
   const long C1 = x1c.size(1), C2 = has2 ? x2c.size(1) : 0;
   const long K0 = rowcat ? C1 : C1 + C2;
   TORCH_CHECK(K0 <= CMAX, "chain fwd: input width must be <= ", CMAX);
-  TORCH_CHECK(!pair || (int)wps.size() == L,
-              "chain fwd pair: packed weights are required for every layer");
+  TORCH_CHECK(!need_packed || (int)wps.size() == L,
+              "chain fwd: packed weights are required for every layer");
   keep.push_back(x1c);
   keep.push_back(x2c);
 
@@ -1084,8 +1158,8 @@ static ChainFwdJob make_fwd_job(
       d.wp[i] = (const u16*)wps[i].data_ptr();
       keep.push_back(wps[i]);
     }
-    TORCH_CHECK(!pair || d.wp[i] != nullptr,
-                "chain fwd pair: no packed weights for layer ", i);
+    TORCH_CHECK(!need_packed || d.wp[i] != nullptr,
+                "chain fwd: no packed weights for layer ", i);
     d.b[i] = bc.data_ptr<float>();
     d.N[i] = (int)N;
     d.act[i] = (i == L - 1) ? (int)act_last : 1;
@@ -1122,12 +1196,13 @@ static ChainFwdJob make_fwd_job(
 // ---------------------------------------------------------------------------
 // Host binding: [y, x_bf16, act_0, ..., act_{L-2}] = mlp_chain_fwd_bf16(
 //     x1, x2_or_empty, ws, bs, act_last, G, out_f32, rm=0, rowcat=0,
-//     save_acts=1)
+//     save_acts=1, wps=[], pipe=0)
 // ws[i]: bf16 [G*N_i, K_i] (or [N,K] / [G,N,K]); bs[i]: f32 [G*N_i].
 // Inputs fp32 or bf16, 2-D [M, C]; x2 may be an empty tensor.  x_bf16 is
 // the converted (concatenated) input, so the backward consumes the same
 // activation list the per-layer path produced.  rm: 0 = auto (by M),
-// 1/2 = force 16/32 rows per workgroup.  rowcat=1 stacks x1/x2 over ROWS
+// 1/2 = force 16/32 rows per workgroup.  pipe: 0 = the 8-wave quad kernel,
+// 1 = k_bf16_chain_fwd_pipe (16-row tiles, a packed buffer for every layer).  rowcat=1 stacks x1/x2 over ROWS
 // (equal widths; M = M1+M2) instead of columns.  save_acts=0 skips the
 // intermediate-activation writes (no-grad forwards, e.g. TD target).
 // ---------------------------------------------------------------------------
@@ -1135,11 +1210,13 @@ static std::vector<torch::Tensor> mlp_chain_fwd_bf16(
     torch::Tensor x1, torch::Tensor x2, std::vector<torch::Tensor> ws,
     std::vector<torch::Tensor> bs, long act_last, long G, long out_f32,
     long rm, long rowcat, long save_acts,
-    std::vector<torch::Tensor> wps) {
+    std::vector<torch::Tensor> wps, long pipe) {
+  TORCH_CHECK(pipe >= 0 && pipe <= 1, "chain fwd: no kernel for pipe=", pipe);
+  TORCH_CHECK(pipe == 0 || rm != 2, "chain fwd pipe: 16-row tiles only");
   std::vector<torch::Tensor> keep, out;
   const ChainFwdJob j = make_fwd_job(x1, x2, ws, bs, act_last, G, out_f32,
-                                     rowcat, save_acts, wps, false, keep,
-                                     out);
+                                     rowcat, save_acts, wps, pipe != 0,
+                                     false, keep, out);
   // RM=1 measured faster at every bench shape (RM=2 halves the L2
   // weight re-read but also halves the workgroups, and these chains are
   // occupancy/latency-bound, not L2-bound — tools/validate_chain_fwd.py
@@ -1149,14 +1226,17 @@ static std::vector<torch::Tensor> mlp_chain_fwd_bf16(
   if (use_rm == 0) use_rm = 1;
   const int TMv = 16 * use_rm;
   dim3 grid((j.M + TMv - 1) / TMv, 1, j.G);
-  if (use_rm == 2)
-    hipLaunchKernelGGL(k_bf16_chain_fwd<2>, grid, dim3(NTHR), 0,
-                       cur_stream3(), j.x1, j.x2, j.C1, j.C2, j.x1f, j.x2f,
-                       j.rowcat, j.M1, j.xsave, j.d, j.y, j.M, j.out_f32);
+#define CHAIN_FWD_LAUNCH(kern, nthr)                                      \
+  hipLaunchKernelGGL(kern, grid, dim3(nthr), 0, cur_stream3(), j.x1,      \
+                     j.x2, j.C1, j.C2, j.x1f, j.x2f, j.rowcat, j.M1,      \
+                     j.xsave, j.d, j.y, j.M, j.out_f32)
+  if (pipe == 1)
+    CHAIN_FWD_LAUNCH((k_bf16_chain_fwd_pipe<16, 2, 4>), 1024);
+  else if (use_rm == 2)
+    CHAIN_FWD_LAUNCH(k_bf16_chain_fwd<2>, NTHR);
   else
-    hipLaunchKernelGGL(k_bf16_chain_fwd<1>, grid, dim3(NTHR), 0,
-                       cur_stream3(), j.x1, j.x2, j.C1, j.C2, j.x1f, j.x2f,
-                       j.rowcat, j.M1, j.xsave, j.d, j.y, j.M, j.out_f32);
+    CHAIN_FWD_LAUNCH(k_bf16_chain_fwd<1>, NTHR);
+#undef CHAIN_FWD_LAUNCH
   return out;
 }
 
@@ -1185,9 +1265,11 @@ static std::vector<std::vector<torch::Tensor>> mlp_chain_fwd_pair_bf16(
   std::vector<std::vector<torch::Tensor>> out(2);
   ChainFwdPair p;
   p.j[0] = make_fwd_job(a_x1, a_x2, a_ws, a_bs, a_act_last, a_G, a_out_f32,
-                        a_rowcat, a_save_acts, a_wps, true, keep, out[0]);
+                        a_rowcat, a_save_acts, a_wps, true, true, keep,
+                        out[0]);
   p.j[1] = make_fwd_job(b_x1, b_x2, b_ws, b_bs, b_act_last, b_G, b_out_f32,
-                        b_rowcat, b_save_acts, b_wps, true, keep, out[1]);
+                        b_rowcat, b_save_acts, b_wps, true, true, keep,
+                        out[1]);
   const int TMv = rm == 2 ? 32 : 16;
   const int tiles = (std::max(p.j[0].M, p.j[1].M) + TMv - 1) / TMv;
   dim3 grid(tiles, 2, std::max(p.j[0].G, p.j[1].G));
@@ -1210,13 +1292,15 @@ void register_chain(pybind11::module_& m) {
         pybind11::arg("youts"), pybind11::arg("K0"), pybind11::arg("acts"),
         pybind11::arg("G"), pybind11::arg("save_dys"),
         pybind11::arg("dx0_lo"),
-        pybind11::arg("wps") = std::vector<torch::Tensor>{});
+        pybind11::arg("wps") = std::vector<torch::Tensor>{},
+        pybind11::arg("pipe") = 0);
   m.def("mlp_chain_fwd_bf16", &chain::mlp_chain_fwd_bf16,
         pybind11::arg("x1"), pybind11::arg("x2"), pybind11::arg("ws"),
         pybind11::arg("bs"), pybind11::arg("act_last"), pybind11::arg("G"),
         pybind11::arg("out_f32"), pybind11::arg("rm") = 0,
         pybind11::arg("rowcat") = 0, pybind11::arg("save_acts") = 1,
-        pybind11::arg("wps") = std::vector<torch::Tensor>{});
+        pybind11::arg("wps") = std::vector<torch::Tensor>{},
+        pybind11::arg("pipe") = 0);
   m.def("mlp_chain_fwd_pair_bf16", &chain::mlp_chain_fwd_pair_bf16,
         pybind11::arg("a_x1"), pybind11::arg("a_x2"), pybind11::arg("a_ws"),
         pybind11::arg("a_bs"), pybind11::arg("a_act_last"),

@@ -27,6 +27,13 @@ def use_chain() -> bool:
     return os.environ.get("DSAC_CHAIN", "1") == "1"
 
 
+def chain_pipe() -> int:
+    """Variant of the chain kernels' packed k-loop, passed to the bindings:
+    1 = the re-shaped pipeline (k_bf16_chain_fwd_pipe / _dx_pipe, default),
+    0 = the 8-wave quad mapping (DSAC_CHAIN_PIPE=0).  Same bits."""
+    return 0 if os.environ.get("DSAC_CHAIN_PIPE", "1") == "0" else 1
+
+
 def frag_numel(rows: int, cols: int, G: int = 1) -> int:
     """bf16 elements of a fragment-packed [G, rows, cols] operand
     (k_bf16_pack_frag: 16x32 tiles of 512 elements).  The forward pack of
@@ -124,7 +131,8 @@ class ManualChain:
                 x1, x2 if x2 is not None else x1.new_empty(0),
                 self.ws16, [b.contiguous() for b in self.bs],
                 int(act_last), self.G, 1 if out_f32 else 0, 0,
-                1 if rowcat else 0, 1 if save_acts else 0, self.fwd_frag)
+                1 if rowcat else 0, 1 if save_acts else 0, self.fwd_frag,
+                chain_pipe())
             return out[0], [out[1]] + list(out[2:])
         if x2 is not None:
             if x1.dtype != x2.dtype:
@@ -152,7 +160,8 @@ class ManualChain:
         if self.chain_mode:
             return ext.mlp_chain_dx_bf16(
                 dy, self._wt, self._youts(acts), acts[0].shape[-1],
-                self._aflags, self.G, 0, int(lo), self.dx_frag)[-1]
+                self._aflags, self.G, 0, int(lo), self.dx_frag,
+                chain_pipe())[-1]
         n = len(self.ws16)
         for i in range(n - 1, 0, -1):
             dy = ext.linear_bwd_dx_bf16(
@@ -184,7 +193,8 @@ class ManualChain:
             return self._dx0_per_layer(ext, dy, acts)[:, dx0_lo:]
         outs = ext.mlp_chain_dx_bf16(
             dy, self._wt, self._youts(acts), acts[0].shape[-1],
-            self._aflags, self.G, 1, int(dx0_lo), self.dx_frag)
+            self._aflags, self.G, 1, int(dx0_lo), self.dx_frag,
+            chain_pipe())
         dx0 = None
         if dx0_lo >= 0:
             dx0 = outs[n][0]
