@@ -93,6 +93,11 @@ class SACEngine:
         self._pcgrad_out: dict = {}
         self._pcgrad_ws: Optional[torch.Tensor] = None
         self._pcgrad_unsupported()
+        # LayerNorm critics: every hidden layer of both Q networks, local
+        # and target, is Linear -> LayerNorm -> ReLU (docs/KERNELS.md
+        # "LayerNorm critics")
+        self.critic_ln = cfg.critic_layer_norm_choice
+        self._ln_unsupported()
         self._build_models()
         self._build_optimizers()
         self._init_grad_clip(max_grad_norm)
@@ -166,7 +171,8 @@ class SACEngine:
             self.local_critic_1, self.local_critic_2, \
                 self.target_critic_1, self.target_critic_2 = (
                     LLCritic(cfg.state_dim, cfg.action_dim,
-                             cfg.critic_hidden_dim, head_width=head).to(dev)
+                             cfg.critic_hidden_dim, head_width=head,
+                             layer_norm=self.critic_ln).to(dev)
                     for _ in range(4))
             self.log_alpha = nn.Parameter(torch.tensor(
                 [float(cfg.log_alpha)], device=dev))
@@ -177,11 +183,13 @@ class SACEngine:
             self.local_critic = Critic(cfg.state_dim, cfg.action_dim,
                                        cfg.critic_hidden_dim,
                                        num_tasks=cfg.num_tasks,
-                                       head_width=head).to(dev)
+                                       head_width=head,
+                                       layer_norm=self.critic_ln).to(dev)
             self.target_critic = Critic(cfg.state_dim, cfg.action_dim,
                                         cfg.critic_hidden_dim,
                                         num_tasks=cfg.num_tasks,
-                                        head_width=head).to(dev)
+                                        head_width=head,
+                                        layer_norm=self.critic_ln).to(dev)
             # per-task log_alpha (reference MT10…MTSAC/src/learner.py:115-121)
             self.log_alpha = nn.Parameter(torch.full(
                 (cfg.num_tasks,), float(cfg.log_alpha), device=dev))
@@ -210,20 +218,49 @@ class SACEngine:
         return self._critic_linears(self.target_critic if target
                                     else self.local_critic)
 
-    def _critic_params(self):
+    def _critic_norm_pairs(self, target: bool = False):
+        """Per hidden layer (Q1.gamma_i, Q2.gamma_i, Q1.beta_i, Q2.beta_i)
+        of the LayerNorm critics; empty with the mode off."""
+        if not self.critic_ln:
+            return []
+        if self.variant in ("sac", "vsac"):
+            n1 = (self.target_critic_1 if target else self.local_critic_1).norm
+            n2 = (self.target_critic_2 if target else self.local_critic_2).norm
+        else:
+            c = self.target_critic if target else self.local_critic
+            n1, n2 = c.Q_norm_1, c.Q_norm_2
+        return list(zip(n1.gamma, n2.gamma, n1.beta, n2.beta))
+
+    def _critic_params(self, target: bool = False):
         """Interleaved per-layer order [Q1.w_i, Q2.w_i, Q1.b_i, Q2.b_i] so
         the flat buffer contains contiguous stacked [2,N,K] weights for the
-        grouped twin-GEMM kernels."""
+        grouped twin-GEMM kernels.  The LayerNorm parameters follow all of
+        them, stacked the same way ([2,N] gamma, then [2,N] beta per hidden
+        layer): the Linear offsets are those of the mode off."""
         out = []
-        for l1, l2 in self._critic_layer_pairs():
+        for l1, l2 in self._critic_layer_pairs(target):
             out += [l1.weight, l2.weight, l1.bias, l2.bias]
+        for quad in self._critic_norm_pairs(target):
+            out += quad
         return out
 
     def _target_params(self):
-        out = []
-        for l1, l2 in self._critic_layer_pairs(target=True):
-            out += [l1.weight, l2.weight, l1.bias, l2.bias]
-        return out
+        return self._critic_params(target=True)
+
+    def _norm_stacks(self, group, target: bool = False):
+        """([2,N] gamma views, [2,N] beta views) into ``group.flat_data``
+        per hidden layer, or (None, None) with the mode off."""
+        if not self.critic_ln:
+            return None, None
+        gs, bs = [], []
+        for g1, g2, b1, b2 in self._critic_norm_pairs(target):
+            for pa, pb, dest in ((g1, g2, gs), (b1, b2, bs)):
+                ia = next(i for i, q in enumerate(group.params) if q is pa)
+                ib = next(i for i, q in enumerate(group.params) if q is pb)
+                off, n = group.offsets[ia], pa.numel()
+                assert group.offsets[ib] == off + n, "stacking needs adjacency"
+                dest.append(group.flat_data[off:off + 2 * n].view(2, n))
+        return gs, bs
 
     def _build_twin_stacks(self, group, pairs, with_grad: bool):
         """Stacked [2,N,K]/[2,N] leaf views into a flat buffer, with .grad
@@ -332,15 +369,20 @@ class SACEngine:
         # re-packed per update (pre-step sets in seg1, the post-Adam
         # critic in seg2)
         pairs = self._critic_layer_pairs()
+        norms = self._critic_norm_pairs()
+        gam, bet = self._norm_stacks(self.critic_group)
         self._critic_chain = ManualChain(
             self._twin_local_bf16, self._twin_local[1], G=2,
             group=self.critic_group,
             w_params=[l1.weight for l1, _ in pairs],
-            b_params=[l1.bias for l1, _ in pairs])
+            b_params=[l1.bias for l1, _ in pairs],
+            gammas=gam, betas=bet, g_params=[q[0] for q in norms],
+            be_params=[q[2] for q in norms])
+        gam_t, bet_t = self._norm_stacks(self.target_group, target=True)
         self._target_chain = ManualChain(
             self._stack_views(self.target_group, self._target_bf16,
                               self._critic_layer_pairs(target=True)),
-            self._twin_target[1], G=2, dx=False)
+            self._twin_target[1], G=2, dx=False, gammas=gam_t, betas=bet_t)
         self._actor_chain = ManualChain(
             self._actor_ws_bf16, bs, group=self.actor_group,
             w_params=ws, b_params=bs)
@@ -414,8 +456,17 @@ class SACEngine:
         from ..ops import has_native, native_enabled
         return t.is_cuda and native_enabled() and has_native()
 
+    def _ln_no_twin_kernels(self) -> None:
+        """The twin forwards below have no LayerNorm: refuse them rather
+        than evaluate a critic without it."""
+        if self.critic_ln:
+            raise NotImplementedError(
+                "critic_layer_norm: the autograd GPU path has no LN "
+                "kernels (the manual bf16 update runs them)")
+
     def _critic_q(self, states, actions):
         if self._use_fused(states):
+            self._ln_no_twin_kernels()
             if self._bf16:
                 x = torch.cat([states, actions], dim=-1)
                 return Fops.twin_mlp_forward_bf16(x, *self._twin_local,
@@ -431,6 +482,7 @@ class SACEngine:
 
     def _target_q(self, states, actions):
         if self._use_fused(states):
+            self._ln_no_twin_kernels()
             if self._bf16:
                 x = torch.cat([states, actions], dim=-1)
                 return Fops.twin_mlp_forward_bf16(x, *self._twin_target,
@@ -492,6 +544,33 @@ class SACEngine:
                    "DSAC_NO_MANUAL=1)")
         if why is not None:
             raise NotImplementedError(f"truncated quantile critics: {why}")
+
+    # -- LayerNorm critics -------------------------------------------------
+    def _ln_unsupported(self, B: Optional[int] = None) -> None:
+        """Raise for the combinations LayerNorm critics do not cover
+        (checked at construction and again per update, where the batch and
+        the environment switches are known)."""
+        if not self.critic_ln:
+            return
+        from ..ops import has_native, native_enabled
+        gpu = self.device.type == "cuda" and native_enabled() \
+            and has_native()
+        why = None
+        if self.variant == "care":
+            why = "CAREEngine has no LayerNorm critic path"
+        elif gpu and self.precision != "bf16":
+            why = ("on a GPU only the bf16 manual-backward path has the LN "
+                   "chain kernels (not the fp32 GPU path)")
+        elif gpu and os.environ.get("DSAC_NO_MANUAL", "0") == "1":
+            why = ("the autograd bf16 path (DSAC_NO_MANUAL=1) has no LN "
+                   "chain kernels")
+        elif gpu and self.pcgrad and B is not None \
+                and (B // self.num_tasks) % 16:
+            why = (f"with pcgrad on a GPU each task's share of the batch "
+                   f"({B} / {self.num_tasks} rows) must be a multiple of "
+                   "the chain kernels' 16-row tile")
+        if why is not None:
+            raise NotImplementedError(f"critic_layer_norm: {why}")
 
     # -- PCGrad ------------------------------------------------------------
     def _pcgrad_unsupported(self, B: Optional[int] = None) -> None:
@@ -661,6 +740,7 @@ class SACEngine:
                     "with prioritized replay")
             self._tqc_unsupported()
         self._pcgrad_unsupported(batch["states"].shape[0])
+        self._ln_unsupported(batch["states"].shape[0])
         out = self._update_tensors(batch)
         if per and self._per is not None:
             self.per_write_back(self._per)
@@ -1397,6 +1477,13 @@ class SACEngine:
                 f"checkpoint critics have head width {saved}, this engine "
                 f"has {max(1, self.tqc_M)} (critic_quantiles = "
                 f"{self.tqc_M}; 1 = scalar critics)")
+        saved_ln = any("norm" in k for k in sd)
+        if saved_ln != self.critic_ln:
+            on = {True: "with", False: "without"}
+            raise ValueError(
+                f"checkpoint critics are {on[saved_ln]} LayerNorm "
+                f"parameters, this engine is built {on[self.critic_ln]} "
+                f"them (critic_layer_norm = {self.critic_ln})")
         self.actor.load_state_dict(ckpt["actor"])
         if self.variant in ("sac", "vsac"):
             self.local_critic_1.load_state_dict(ckpt["local_critic_1"])

@@ -125,6 +125,11 @@ class SACConfig:
     # (a cfg without the key): DSAC_PCGRAD=1, else off.  See docs/KERNELS.md
     # "PCGrad".
     pcgrad: Optional[bool] = None
+    # net-new (the reference has none): LayerNorm critics.  Every hidden
+    # layer of both Q networks, local and target, is Linear -> LayerNorm ->
+    # ReLU.  None (a cfg without the key): DSAC_CRITIC_LN=1, else off.  See
+    # docs/KERNELS.md "LayerNorm critics".
+    critic_layer_norm: Optional[bool] = None
     # CARE-only block (reference cfg "encoder"):
     encoder: Optional[Dict[str, Any]] = None
     use_modified_care: bool = False
@@ -196,6 +201,17 @@ class SACConfig:
         env = os.environ.get("DSAC_PCGRAD", "")
         if env not in ("", "0", "1"):
             raise ValueError(f"DSAC_PCGRAD must be 0 or 1, got {env!r}")
+        return env == "1"
+
+    @property
+    def critic_layer_norm_choice(self) -> bool:
+        """The cfg's ``critic_layer_norm`` where set, else ``DSAC_CRITIC_LN``
+        (``1`` = on; unset, empty or ``0`` = off)."""
+        if self.critic_layer_norm is not None:
+            return bool(self.critic_layer_norm)
+        env = os.environ.get("DSAC_CRITIC_LN", "")
+        if env not in ("", "0", "1"):
+            raise ValueError(f"DSAC_CRITIC_LN must be 0 or 1, got {env!r}")
         return env == "1"
 
     @property
@@ -282,6 +298,11 @@ class SACConfig:
                 raise ValueError(
                     f"pcgrad must be true or false, got {cfg['pcgrad']!r}")
             c.pcgrad = cfg["pcgrad"]
+        if "critic_layer_norm" in cfg:
+            if not isinstance(cfg["critic_layer_norm"], bool):
+                raise ValueError("critic_layer_norm must be true or false, "
+                                 f"got {cfg['critic_layer_norm']!r}")
+            c.critic_layer_norm = cfg["critic_layer_norm"]
         if "use_modified_care" in cfg:
             c.use_modified_care = bool(cfg["use_modified_care"])
         if "encoder" in cfg:

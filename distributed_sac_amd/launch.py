@@ -67,6 +67,10 @@ def main():
                     help="PCGrad gradient surgery between the per-task "
                          "critic and actor gradients, mtsac only (default: "
                          "the cfg's pcgrad, else DSAC_PCGRAD, else off)")
+    ap.add_argument("--critic-layer-norm", action="store_true", default=None,
+                    help="LayerNorm after every hidden critic layer "
+                         "(default: the cfg's critic_layer_norm, else "
+                         "DSAC_CRITIC_LN, else off)")
     # eval mode
     ap.add_argument("--eval", action="store_true")
     ap.add_argument("--checkpoint", default=None)
@@ -92,8 +96,11 @@ def main():
         cfg.critic_quantiles_drop = args.critic_quantiles_drop
     if args.pcgrad:
         cfg.pcgrad = True
+    if args.critic_layer_norm:
+        cfg.critic_layer_norm = True
     cfg.critic_quantiles_choice   # validate before anything starts
     cfg.pcgrad_choice
+    cfg.critic_layer_norm_choice
 
     env_fn = default_env_fn
     if args.env:

@@ -15,15 +15,17 @@ import torch
 import torch.nn as nn
 
 from ..ops import functional as Fops
-from .mlp import build_mlp, weights_init
+from .mlp import LNParams, build_mlp, linears_of, weights_init
 
 
 class Critic(nn.Module):
-    """Twin Q on [mtobs || action]; keys ``Q_function_{1,2}.{0,2,4,6}.*``."""
+    """Twin Q on [mtobs || action]; keys ``Q_function_{1,2}.{0,2,4,6}.*``.
+    ``layer_norm``: every hidden layer is Linear -> LayerNorm -> ReLU, the
+    LayerNorm parameters under the extra keys ``Q_norm_{1,2}.*``."""
 
     def __init__(self, state_dim: int, action_dim: int,
                  hidden_dims: List[int], num_tasks: int = 0,
-                 head_width: int = 1):
+                 head_width: int = 1, layer_norm: bool = False):
         super().__init__()
         self.state_dim = state_dim
         self.num_tasks = num_tasks
@@ -35,9 +37,18 @@ class Critic(nn.Module):
         self.Q_function_2 = build_mlp(in_dim, head_width, hidden_dims)
         self.Q_function_1.apply(weights_init)
         self.Q_function_2.apply(weights_init)
+        self.layer_norm = bool(layer_norm)
+        if self.layer_norm:
+            self.Q_norm_1 = LNParams(hidden_dims)
+            self.Q_norm_2 = LNParams(hidden_dims)
 
     def forward(self, mtobss: torch.Tensor, action: torch.Tensor):
         x = torch.cat([mtobss, action], dim=-1)
+        if self.layer_norm:
+            return tuple(
+                Fops.ln_mlp_forward(x, *linears_of(q), n.gamma, n.beta)
+                for q, n in ((self.Q_function_1, self.Q_norm_1),
+                             (self.Q_function_2, self.Q_norm_2)))
         return self.Q_function_1(x), self.Q_function_2(x)
 
     def cal_loss(self, mtobss, action, td_target_values,
@@ -68,10 +79,13 @@ class Critic(nn.Module):
 
 class LLCritic(nn.Module):
     """Single-Q MLP on [state || action] — keys ``first_layer.*``,
-    ``layer_module.{0,1}.*`` (LunarLander…/src/model.py:92-142)."""
+    ``layer_module.{0,1}.*`` (LunarLander…/src/model.py:92-142).
+    ``layer_norm``: every hidden layer is Linear -> LayerNorm -> ReLU, the
+    LayerNorm parameters under the extra keys ``norm.*``."""
 
     def __init__(self, state_dim: int, action_dim: int,
-                 hidden_dim: List[int] = (256, 256), head_width: int = 1):
+                 hidden_dim: List[int] = (256, 256), head_width: int = 1,
+                 layer_norm: bool = False):
         super().__init__()
         self.state_dim = state_dim
         self.action_dim = action_dim
@@ -81,11 +95,17 @@ class LLCritic(nn.Module):
         self.layer_module = nn.ModuleList(
             [nn.Linear(i, o) for i, o in zip(dims[:-1], dims[1:])])
         self.apply(weights_init)
+        self.layer_norm = bool(layer_norm)
+        if self.layer_norm:
+            self.norm = LNParams(list(hidden_dim))
 
     def forward(self, state: torch.Tensor, action: torch.Tensor):
         x = torch.cat([state, action], dim=-1)
         ws = [self.first_layer.weight] + [m.weight for m in self.layer_module]
         bs = [self.first_layer.bias] + [m.bias for m in self.layer_module]
+        if self.layer_norm:
+            return Fops.ln_mlp_forward(x, ws, bs, self.norm.gamma,
+                                       self.norm.beta)
         return Fops.mlp_forward(x, ws, bs)
 
     def cal_loss(self, state, action, td_target_values):

@@ -39,6 +39,26 @@ class FusedMLP(nn.Sequential):
         return Fops.mlp_forward(x, ws, bs)
 
 
+class LNParams(nn.Module):
+    """gamma (ones) and beta (zeros) of the LayerNorm after each hidden
+    layer of an MLP.  Held beside the Linear stack, not inside it, so that
+    the stack's state_dict keys keep their names and indices; keys
+    ``gamma.{i}`` / ``beta.{i}``."""
+
+    def __init__(self, hidden_dims: List[int]):
+        super().__init__()
+        self.gamma = nn.ParameterList(
+            [nn.Parameter(torch.ones(d)) for d in hidden_dims])
+        self.beta = nn.ParameterList(
+            [nn.Parameter(torch.zeros(d)) for d in hidden_dims])
+
+
+def linears_of(mlp: nn.Module):
+    """(weights, biases) of the Linear layers of a Sequential."""
+    lins = [m for m in mlp if isinstance(m, nn.Linear)]
+    return [m.weight for m in lins], [m.bias for m in lins]
+
+
 def build_mlp(input_dim: int, output_dim: int, hidden_dims: List[int]) -> FusedMLP:
     """Reference build_mlp layout: no activation on the output layer."""
     layers: List[nn.Module] = []

@@ -3235,6 +3235,7 @@ void register_f32_chain(pybind11::module_& m);
 void register_f32_chain_bwd(pybind11::module_& m);
 void register_tqc(pybind11::module_& m);
 void register_pcgrad(pybind11::module_& m);
+void register_ln_chain(pybind11::module_& m);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   register_shm_ring(mod);
@@ -3244,6 +3245,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   register_f32_chain_bwd(mod);
   register_tqc(mod);
   register_pcgrad(mod);
+  register_ln_chain(mod);
   mod.def("linear_act_fwd", &linear_act_fwd, "fused GEMM+bias+act forward");
   mod.def("linear_act_fwd_g", &linear_act_fwd_g, "grouped (twin) variant");
   mod.def("linear_bwd_dx", &linear_bwd_dx, "GEMM backward dX (fused mask)");

@@ -7,7 +7,9 @@ W^T shape carriers of the dx kernel and the chain's word offsets into its
 flat gradient.  ``forward`` / ``input_grad`` / ``backward`` hide the two
 kernel modes: the fused chain kernels (default) and the per-layer kernels
 (``DSAC_CHAIN=0``).  Both issue the same math; the per-layer mode needs no
-packed weights.
+packed weights.  A chain built with ``gammas`` / ``betas`` is a LayerNorm
+chain (hidden layers Linear -> LayerNorm -> ReLU): it always runs the fused
+LN kernels of ln_chain.hip.
 """
 
 from __future__ import annotations
@@ -67,18 +69,37 @@ class ManualChain:
     Q2 follows it) fixes the flat-gradient offsets; a chain that is never
     differentiated passes none.  ``dx=False`` skips the dx-side buffers
     (target twin).  ``always_chain`` pins the chain kernels regardless of
-    DSAC_CHAIN (context encoder)."""
+    DSAC_CHAIN (context encoder).
+
+    ``gammas`` / ``betas`` (fp32 [G,N] per hidden layer, views of the flat
+    master buffer) make it a LayerNorm chain; ``g_params`` / ``be_params``
+    fix their flat-gradient offsets like ``w_params``.  ``acts`` of an LN
+    chain is [bf16 input, h per hidden layer, xhat per hidden layer, rstd
+    per hidden layer]."""
 
     def __init__(self, ws16: Sequence[torch.Tensor],
                  bs: Sequence[torch.Tensor], G: int = 1,
                  group: Optional[FlatParams] = None,
                  w_params: Sequence[torch.Tensor] = (),
                  b_params: Sequence[torch.Tensor] = (),
-                 dx: bool = True, always_chain: bool = False):
+                 dx: bool = True, always_chain: bool = False,
+                 gammas: Optional[Sequence[torch.Tensor]] = None,
+                 betas: Optional[Sequence[torch.Tensor]] = None,
+                 g_params: Sequence[torch.Tensor] = (),
+                 be_params: Sequence[torch.Tensor] = (),
+                 eps: float = 1e-5):
         self.ws16 = list(ws16)
         self.bs = list(bs)
         self.G = int(G)
-        self._always_chain = always_chain
+        self.ln = gammas is not None
+        self.gammas = list(gammas) if self.ln else None
+        self.betas = list(betas) if self.ln else None
+        self.eps = float(eps)
+        if self.ln and not (len(self.gammas) == len(self.betas)
+                            == len(self.ws16) - 1 >= 1):
+            raise ValueError("an LN chain needs gamma and beta for each of "
+                             "its (one or more) hidden layers")
+        self._always_chain = always_chain or self.ln
         dev = self.ws16[0].device
 
         def buf(*shape):
@@ -103,6 +124,8 @@ class ManualChain:
                                        if q is p)] for p in ps]
         self.w_offs: List[int] = offs(w_params)
         self.b_offs: List[int] = offs(b_params)
+        self.g_offs: List[int] = offs(g_params)
+        self.be_offs: List[int] = offs(be_params)
 
     @property
     def chain_mode(self) -> bool:
@@ -126,6 +149,15 @@ class ManualChain:
         (y, acts): y is [M,N] or [G,M,N]; acts = [bf16 input, hidden
         activations...], what input_grad/backward consume."""
         ext = native()
+        if self.ln:
+            if act_last:
+                raise NotImplementedError("LN chain: linear output layer only")
+            out = ext.mlp_chain_ln_fwd_bf16(
+                x1, x2 if x2 is not None else x1.new_empty(0),
+                self.fwd_frag, [b.contiguous() for b in self.bs],
+                self.gammas, self.betas, self.G, 1 if out_f32 else 0,
+                1 if rowcat else 0, 1 if save_acts else 0, self.eps)
+            return out[0], list(out[1:])
         if self.chain_mode:
             out = ext.mlp_chain_fwd_bf16(
                 x1, x2 if x2 is not None else x1.new_empty(0),
@@ -157,6 +189,8 @@ class ManualChain:
         ``lo:``, per group [G,M,K0-lo] — the per-layer mode returns the
         groups already summed, [M,K0-lo]."""
         ext = native()
+        if self.ln:
+            return self._ln_dx(ext, dy, acts, 0, int(lo))[-1]
         if self.chain_mode:
             return ext.mlp_chain_dx_bf16(
                 dy, self._wt, self._youts(acts), acts[0].shape[-1],
@@ -169,6 +203,14 @@ class ManualChain:
                 self._aflags[i], self.G, 0)
         return self._dx0_per_layer(ext, dy, acts)[:, lo:].float()
 
+    def _ln_dx(self, ext, dy, acts, want_dw: int, dx0_lo: int):
+        """k_bf16_chain_ln_dx on an LN chain's saved ``acts``."""
+        h = len(self.ws16) - 1
+        return ext.mlp_chain_ln_dx_bf16(
+            dy, self.dx_frag, list(acts[1:1 + h]),
+            list(acts[1 + h:1 + 2 * h]), list(acts[1 + 2 * h:1 + 3 * h]),
+            self.gammas, acts[0].shape[-1], self.G, want_dw, dx0_lo)
+
     def _dx0_per_layer(self, ext, dy, acts):
         n = len(self.ws16)
         return ext.linear_bwd_dx_bf16(
@@ -179,10 +221,14 @@ class ManualChain:
     def backward(self, dy, acts, arena, S, chunk, *, rows=None, dx0_lo=-1):
         """Full backward: dW/db split-K partials into ``arena`` at the
         chain's flat-grad offsets.  ``rows`` selects a row range of
-        batched activations.  With ``dx0_lo >= 0`` returns the bf16
-        gradient w.r.t. input columns ``dx0_lo:``, summed over groups."""
+        batched activations (an LN chain takes none).  With ``dx0_lo >= 0``
+        returns the bf16 gradient w.r.t. input columns ``dx0_lo:``, summed
+        over groups."""
         ext = native()
         n = len(self.ws16)
+        if self.ln:
+            return self._ln_backward(ext, dy, acts, arena, S, chunk, rows,
+                                     int(dx0_lo))
         if rows is not None:
             acts = [a[..., rows, :] for a in acts]
         if not self.chain_mode:
@@ -205,6 +251,27 @@ class ManualChain:
                                self.w_offs, self.b_offs, self.G, S, chunk)
         return dx0
 
+    def _ln_backward(self, ext, dy, acts, arena, S, chunk, rows, dx0_lo):
+        """backward() of an LN chain: the dx walk (dz per layer and the
+        block partials of d beta / d gamma), the grouped dW/db launch on
+        dz, and one fold of the partials into the arena rows."""
+        if rows is not None:
+            raise NotImplementedError("LN chain: no row range in backward")
+        if chunk % 16:
+            raise ValueError(
+                f"LN chain: the arena's row chunk ({chunk}) must be a "
+                "multiple of the 16-row tile of the chain kernels")
+        n = len(self.ws16)
+        outs = self._ln_dx(ext, dy, acts, 1, dx0_lo)
+        dx0 = None
+        if dx0_lo >= 0:
+            dx0 = outs[-1].sum(dim=0).to(torch.bfloat16)
+        ext.dwdb_grouped_arena(list(outs[:n]), list(acts[:n]), arena,
+                               self.w_offs, self.b_offs, self.G, S, chunk)
+        ext.ln_dgb_fold(list(outs[n:2 * n - 1]), arena, self.g_offs,
+                        self.be_offs, self.G, S, chunk, dy.shape[-2])
+        return dx0
+
 
 def use_pair_fwd() -> bool:
     """Two independent forward chains in one launch (forward_pair).
@@ -218,10 +285,12 @@ def forward_pair(a, b):
     given as ``(chain, args, kwargs)``; returns the two results.  With both
     chains on the chain kernels this is one k_bf16_chain_fwd_pair launch
     (same bits; a ``save_acts=False`` job's acts[0] comes back empty),
-    otherwise the two forward calls in the given order.  DSAC_PAIR_RM=2
+    otherwise (an LN chain among them: there is no LN pair kernel) the two
+    forward calls in the given order.  DSAC_PAIR_RM=2
     selects 32-row tiles (measurement only)."""
     (ca, args_a, kw_a), (cb, args_b, kw_b) = a, b
-    if not (ca.chain_mode and cb.chain_mode and use_pair_fwd()):
+    if ca.ln or cb.ln or not (ca.chain_mode and cb.chain_mode
+                              and use_pair_fwd()):
         return ca.forward(*args_a, **kw_a), cb.forward(*args_b, **kw_b)
     rm = 2 if os.environ.get("DSAC_PAIR_RM", "1") == "2" else 1
     outs = native().mlp_chain_fwd_pair_bf16(

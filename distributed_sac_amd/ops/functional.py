@@ -261,6 +261,20 @@ def mlp_forward(x: torch.Tensor,
     return torch_ref.mlp_forward(x, weights, biases)
 
 
+def ln_mlp_forward(x: torch.Tensor, weights, biases, gammas, betas,
+                   eps: float = torch_ref.LN_EPS) -> torch.Tensor:
+    """LayerNorm MLP (hidden layers Linear -> LayerNorm -> ReLU, linear
+    output).  The autograd path is the torch one, for CPU tensors; on a GPU
+    the LN chain kernels are driven by ops.chain.ManualChain (the manual
+    bf16 update), and nothing stands in for them here."""
+    if _use_native(x):
+        raise NotImplementedError(
+            "critic_layer_norm: no autograd GPU path, the LN chain kernels "
+            "run in the manual bf16 update only")
+    return torch_ref.ln_mlp_forward(x, list(weights), list(biases),
+                                    list(gammas), list(betas), eps)
+
+
 def twin_mlp_forward(x: torch.Tensor, stacked_ws, stacked_bs,
                      x2: Optional[torch.Tensor] = None):
     """Both Q heads in one grouped launch per layer.  stacked_ws[i] is a

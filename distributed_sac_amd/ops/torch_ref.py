@@ -55,6 +55,30 @@ def mlp_forward(x: torch.Tensor,
     return x
 
 
+LN_EPS = 1e-5
+
+
+def ln_mlp_forward(x: torch.Tensor, weights: Sequence[torch.Tensor],
+                   biases: Sequence[torch.Tensor],
+                   gammas: Sequence[torch.Tensor],
+                   betas: Sequence[torch.Tensor],
+                   eps: float = LN_EPS) -> torch.Tensor:
+    """LayerNorm MLP: every hidden layer is Linear -> LayerNorm -> ReLU, the
+    output layer linear.  The contract of the LN chain kernels
+    (docs/KERNELS.md "LayerNorm critics"), in the dtype of ``x``: per row
+    ``mu = mean z``, then ``var = mean (z - mu)^2`` (two passes, biased),
+    ``xhat = (z - mu) rsqrt(var + eps)``, ``h = relu(xhat gamma + beta)``.
+    Autograd through these lines is the kernels' backward."""
+    n = len(weights)
+    for i, (w, b) in enumerate(zip(weights, biases)):
+        x = F.linear(x, w, b)
+        if i < n - 1:
+            d = x - x.mean(dim=-1, keepdim=True)
+            var = (d * d).mean(dim=-1, keepdim=True)
+            x = torch.relu(d * torch.rsqrt(var + eps) * gammas[i] + betas[i])
+    return x
+
+
 def squashed_gaussian(mu: torch.Tensor, log_std: torch.Tensor,
                       eps: torch.Tensor, k: float):
     """Tanh-squashed Gaussian sample + summed log-prob.
@@ -694,6 +718,92 @@ def gemm_bound_ratio(out: torch.Tensor, ref: torch.Tensor,
     ok = err <= bound                # False for NaN
     ratio = torch.where(bound > 0, err / bound, torch.zeros_like(err))
     return torch.where(ok, ratio, torch.full_like(err, float("inf")))
+
+
+# ---------------------------------------------------------------------------
+# LayerNorm layer oracles for the LN chain kernels, in the manner of
+# gemm_oracle: float64 values from the kernel's own operands, each with a
+# bound that follows the kernel's fp32 arithmetic step by step.  u = 2^-24 is
+# the fp32 unit roundoff; a sum of N fp32 terms in any order plus the scaling
+# by 1/N stays within (N + 3) u of its exact value, relative to the sum of
+# magnitudes.  The bounds are for the value BEFORE the bf16 rounding of a
+# bf16 output: gemm_bound_ratio adds that.
+# ---------------------------------------------------------------------------
+
+LN_U = 2.0 ** -24
+
+
+@torch.no_grad()
+def ln_fwd_oracle(a, w, bias, gamma, beta, eps: float = LN_EPS):
+    """One hidden LN layer from its bf16 input ``a [.., M, K]``, bf16
+    weights ``w [.., N, K]`` and fp32 ``bias``, ``gamma``, ``beta``
+    ``[.., N]``: ``(h, xhat, rstd)`` in float64 and their bounds
+    ``(tol_h, tol_xhat, tol_rstd)``."""
+    z, tz = gemm_oracle(a, w, bias)      # fp32 accumulator + bias, unrounded
+    N = z.shape[-1]
+    gam, bet = gamma.double().unsqueeze(-2), beta.double().unsqueeze(-2)
+    mean = lambda t: t.mean(dim=-1, keepdim=True)   # noqa: E731
+    nu = (N + 3) * LN_U
+    mu = mean(z)
+    d = z - mu
+    var = mean(d * d)
+    rstd = (var + eps).rsqrt()
+    xhat = d * rstd
+    y = xhat * gam + bet
+    e_mu = mean(tz) + nu * mean(z.abs())
+    e_d = tz + e_mu + 2 * LN_U * d.abs()
+    e_sq = 2 * d.abs() * e_d + e_d * e_d
+    e_var = mean(e_sq) + nu * (var + mean(e_sq))
+    # 1 / sqrt is convex and decreasing: the error is largest downwards
+    r_hi = ((var - e_var).clamp(min=0.0) + eps).rsqrt()
+    e_r = (r_hi - rstd) + 4 * LN_U * r_hi
+    e_x = e_d * r_hi + d.abs() * e_r + 2 * LN_U * xhat.abs()
+    e_h = e_x * gam.abs() + 3 * LN_U * ((xhat * gam).abs() + bet.abs())
+    return (y.clamp(min=0.0), xhat, rstd.squeeze(-1)), \
+        (e_h, e_x, e_r.squeeze(-1))
+
+
+@torch.no_grad()
+def ln_bwd_oracle(dz_next, w_next, h, xhat, rstd, gamma):
+    """The backward of one hidden LN layer from the kernel's own bf16
+    ``dz_next [.., M, N2]`` (gradient at the next layer's linear output),
+    that layer's bf16 weights ``w_next [.., N2, N]`` and the saved bf16
+    ``h``, ``xhat`` ``[.., M, N]``, fp32 ``rstd [.., M]``, ``gamma
+    [.., N]``.  Returns ``(dz, tol_dz)`` and the per-row terms of the
+    parameter gradients with their bounds, ``(dh, tol_dh)`` and
+    ``(dh xhat, tol)``: d beta / d gamma of a row slice are their column
+    sums (:func:`ln_colsum`)."""
+    dA, tA = gemm_oracle(dz_next, w_next.transpose(-1, -2))
+    N = dA.shape[-1]
+    mask = h.double() > 0
+    zero = torch.zeros_like(dA)
+    x = xhat.double()
+    gam = gamma.double().unsqueeze(-2)
+    rs = rstd.double().unsqueeze(-1)
+    mean = lambda t: t.mean(dim=-1, keepdim=True)   # noqa: E731
+    nu = (N + 3) * LN_U
+    dh, e_dh = torch.where(mask, dA, zero), torch.where(mask, tA, zero)
+    g = dh * gam
+    e_g = e_dh * gam.abs() + LN_U * g.abs()
+    m1, m2 = mean(g), mean(g * x)
+    e_m1 = mean(e_g) + nu * mean(g.abs())
+    e_m2 = mean(e_g * x.abs()) + (nu + LN_U) * mean((g * x).abs())
+    dz = rs * (g - m1 - x * m2)
+    e_dz = rs * (e_g + e_m1 + x.abs() * e_m2) \
+        + 4 * LN_U * rs * (g.abs() + m1.abs() + (x * m2).abs())
+    return (dz, e_dz), (dh, e_dh), \
+        (dh * x, e_dh * x.abs() + LN_U * (dh * x).abs())
+
+
+@torch.no_grad()
+def ln_colsum(term, tol, lo: int, hi: int):
+    """Column sums over rows ``[lo, hi)`` of per-row terms ``[.., M, N]``
+    and the bound of an fp32 sum of them in any order (the 16-row block
+    partials, then the blocks): ``(ref, tol)``, both ``[.., N]``."""
+    t, e = term[..., lo:hi, :], tol[..., lo:hi, :]
+    n = hi - lo
+    return t.sum(dim=-2), e.sum(dim=-2) \
+        + (n + 2) * GEMM_ULP * t.abs().sum(dim=-2) + GEMM_FLOOR
 
 
 def pack_frag_ref(w: torch.Tensor, G: int, dx: bool = False) -> torch.Tensor:

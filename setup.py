@@ -29,7 +29,8 @@ setup(
                      "distributed_sac_amd/ops/_hip/f32_chain.hip",
                      "distributed_sac_amd/ops/_hip/f32_chain_bwd.hip",
                      "distributed_sac_amd/ops/_hip/tqc.hip",
-                     "distributed_sac_amd/ops/_hip/pcgrad.hip"],
+                     "distributed_sac_amd/ops/_hip/pcgrad.hip",
+                     "distributed_sac_amd/ops/_hip/ln_chain.hip"],
             extra_compile_args={
                 "cxx": ["-O3"],
                 "nvcc": ["-O3", "--offload-arch=gfx950"],
