@@ -43,6 +43,8 @@ from .sac import SACEngine
 
 
 class CAREEngine(SACEngine):
+    _ref_weighting_name = "weighted_loss_mode='reference'"
+
     def __init__(self, cfg: SACConfig, device="cpu",
                  precision: Optional[str] = None,
                  max_grad_norm: Optional[float] = None):
@@ -188,13 +190,9 @@ class CAREEngine(SACEngine):
     def update_tensors(self, batch: Dict[str, torch.Tensor]):
         if "is_weights" in batch:
             self._per_unsupported()
-        if self._use_fused(batch["states"]):
-            if self.degenerate_w and self.use_weighted_loss:
-                raise RuntimeError(
-                    "weighted_loss_mode='reference' is a CPU strict-parity "
-                    "mode; the fused HIP kernels implement corrected "
-                    "weighting (docs/PARITY.md)")
-            return self._update_tensors_fused(batch)
+        return self._update_tensors(batch)
+
+    def _update_tensors_torch(self, batch):
         states, actions = batch["states"], batch["actions"]
         rewards, next_states, dones = (batch["rewards"], batch["next_states"],
                                        batch["dones"])
@@ -363,39 +361,17 @@ class CAREEngine(SACEngine):
             zc = z_context
         return torch.cat([zc, z_enc], dim=1)
 
-    def _twin_fwd(self, x, which: str, x2=None):
-        """x2: the heads' input is [x || x2].  fp32 hands both to
-        twin_mlp_forward (torch.cat, or with DSAC_F32_CHAIN=1 the chain
-        kernel's loader); bf16 concatenates here."""
-        if self._bf16:
-            if x2 is not None:
-                x = torch.cat([x, x2], dim=-1)
-            if which == "target":
-                return Fops.twin_mlp_forward_bf16(x, *self._twin_target,
-                                                  self._target_chain.ws16)
-            if which == "frozen":
-                return Fops.twin_mlp_forward_bf16(x,
-                                                  *self._twin_local_frozen,
-                                                  self._twin_local_bf16)
-            return Fops.twin_mlp_forward_bf16(x, *self._twin_local,
-                                              self._twin_local_bf16)
-        if which == "target":
-            return Fops.twin_mlp_forward(x, *self._twin_target, x2=x2)
-        if which == "frozen":
-            return Fops.twin_mlp_forward(x, *self._twin_local_frozen, x2=x2)
-        return Fops.twin_mlp_forward(x, *self._twin_local, x2=x2)
+    @property
+    def _manual_ok(self) -> bool:
+        return self._se_fast and (self.use_modified_care
+                                  or self._ctx_chain is not None)
 
-    def _update_tensors_fused(self, batch):
+    def _update_tensors_fused(self, batch, path: str):
         """GPU path: fused losses + twin-head grouped GEMMs (bf16 mirrors
         when enabled).  Forwards whose grads the reference discards run
         under no_grad (see module doc); the actor head runs ONE batched
         pass over cat(next, states) like the SAC engine (the actor-side
         state encoder is no-grad in both halves)."""
-        manual_ok = self._se_fast and (
-            self.use_modified_care
-            or self._ctx_chain is not None)
-        if manual_ok and os.environ.get("DSAC_NO_MANUAL", "0") != "1":
-            return self._update_tensors_manual(batch)
         from ..ops import native
         states, actions = batch["states"], batch["actions"]
         rewards, next_states, dones = (batch["rewards"], batch["next_states"],
@@ -426,7 +402,7 @@ class CAREEngine(SACEngine):
         ws, bs = self._actor_weights()
         enc_actor_in = (enc_cat.detach() if self._se_fast
                         else enc_cat)
-        if self._bf16:
+        if path == "bf16-autograd":
             mu_lsr = Fops.mlp_forward_bf16(enc_actor_in, ws, bs,
                                            self._actor_ws_bf16,
                                            grad_row_start=B)
@@ -445,7 +421,7 @@ class CAREEngine(SACEngine):
                                           z_context)
             else:
                 enc_t = self.target_critic.encode(next_states, z_context)
-            q1_t, q2_t = self._twin_fwd(enc_t, "target", x2=na)
+            q1_t, q2_t = self._twin_fwd(enc_t, na, "target", path)
             y = native().td_target_mt(rewards, dones, q1_t, q2_t, nlp,
                                       states, self.log_alpha.detach(), T,
                                       self.gamma, self.reward_scale)
@@ -454,7 +430,7 @@ class CAREEngine(SACEngine):
             enc = enc_cat[B:]
         else:
             enc = self.local_critic.encode(states, z_context)
-        q1, q2 = self._twin_fwd(enc, "local", x2=actions)
+        q1, q2 = self._twin_fwd(enc, actions, "local", path)
         l1, l2 = Fops.critic_loss(q1, q2, y, states, self.log_alpha.detach(),
                                   T, use_w)
         q_loss = l1 + l2
@@ -469,7 +445,7 @@ class CAREEngine(SACEngine):
             else:
                 enc_c = self.local_critic.encode(states, zc_d,
                                                  detach_z_encs=True)
-        aq1, aq2 = self._twin_fwd(enc_c, "frozen", x2=sa)
+        aq1, aq2 = self._twin_fwd(enc_c, sa, "frozen", path)
         policy_loss, loss_log_alpha, entropy = Fops.actor_alpha_loss(
             aq1, aq2, lp, ls, states, self.log_alpha, T, use_w, self.H_bar_f)
         (policy_loss + loss_log_alpha).backward()

@@ -35,6 +35,7 @@ from ..ops import functional as Fops
 from ..ops import torch_ref
 from ..ops.chain import ManualChain, forward_pair, pack_chains
 from ..ops.flat import FlatParams, FusedAdam, flat_polyak_
+from . import support
 
 
 class SACEngine:
@@ -84,7 +85,6 @@ class SACEngine:
         # truncated quantile critics: M atoms per Q network (0 = scalar
         # critics), tqc_drop atoms per network cut from the pooled target
         self.tqc_M, self.tqc_drop = cfg.critic_quantiles_choice
-        self._tqc_unsupported()
         # PCGrad gradient surgery between the per-task gradients of the
         # critic and of the actor group (docs/KERNELS.md "PCGrad")
         self.pcgrad = cfg.pcgrad_choice
@@ -92,11 +92,12 @@ class SACEngine:
         self._pcgrad_updates = 0
         self._pcgrad_out: dict = {}
         self._pcgrad_ws: Optional[torch.Tensor] = None
-        self._pcgrad_unsupported()
         # LayerNorm critics: every hidden layer of both Q networks, local
         # and target, is Linear -> LayerNorm -> ReLU (docs/KERNELS.md
         # "LayerNorm critics")
         self.critic_ln = cfg.critic_layer_norm_choice
+        self._tqc_unsupported()
+        self._pcgrad_unsupported()
         self._ln_unsupported()
         self._build_models()
         self._build_optimizers()
@@ -451,10 +452,59 @@ class SACEngine:
         self.critic_group.rebind_grads()
         self.alpha_group.rebind_grads()
 
-    # ------------------------------------------------------------------
-    def _use_fused(self, t: torch.Tensor) -> bool:
+    # -- update path and mode support (the rules: algo/support.py) -------
+    _manual_ok = True  # CAREEngine: its manual update's preconditions
+
+    def _update_path(self, t: Optional[torch.Tensor] = None) -> str:
+        """The update path (:func:`support.update_path`) for tensors on
+        ``t``'s device, or on the engine's without ``t``.  The environment
+        switches are read at every call."""
         from ..ops import has_native, native_enabled
-        return t.is_cuda and native_enabled() and has_native()
+        on_gpu = self.device.type == "cuda" if t is None else t.is_cuda
+        return support.update_path(
+            on_gpu, self.precision,
+            on_gpu and native_enabled() and has_native(),
+            os.environ.get("DSAC_NO_MANUAL", "0") == "1", self._manual_ok)
+
+    def _refuse(self, mode: str, on=True, B: Optional[int] = None,
+                per: bool = False) -> None:
+        """Raise for the combinations the opt-in ``mode`` does not cover, if
+        it is ``on`` (checked at construction and again per update, where
+        the batch, the attached group and the environment switches are
+        known)."""
+        if not on:
+            return
+        why = support.unsupported(mode, {
+            "variant": self.variant,
+            "ddp": self.ddp is not None and getattr(self.ddp, "enabled", True),
+            "ref_weighting": self.degenerate_w and self.use_weighted_loss,
+            "path": self._update_path(), "T": self.num_tasks, "B": B,
+            "per": per or self._per is not None, "pcgrad": self.pcgrad,
+            "krng": os.environ.get("DSAC_KRNG", "1") == "1"})
+        if why is not None:
+            raise NotImplementedError(why)
+
+    def _per_unsupported(self) -> None:
+        self._refuse("prioritized replay")
+
+    def _tqc_unsupported(self, per: bool = False) -> None:
+        self._refuse("truncated quantile critics", self.tqc_M, per=per)
+
+    def _ln_unsupported(self, B: Optional[int] = None) -> None:
+        self._refuse("critic_layer_norm", self.critic_ln, B)
+
+    def _pcgrad_unsupported(self, B: Optional[int] = None) -> None:
+        self._refuse("pcgrad", self.pcgrad, B)
+
+    _ref_weighting_name = \
+        "weighted_loss_mode='reference' (degenerate broadcast)"
+
+    def _ref_weighting_is_cpu_only(self) -> None:
+        if self.degenerate_w and self.use_weighted_loss:
+            raise RuntimeError(
+                f"{self._ref_weighting_name} is a CPU strict-parity mode; "
+                "the fused HIP kernels implement corrected weighting "
+                "(docs/PARITY.md)")
 
     def _ln_no_twin_kernels(self) -> None:
         """The twin forwards below have no LayerNorm: refuse them rather
@@ -464,31 +514,36 @@ class SACEngine:
                 "critic_layer_norm: the autograd GPU path has no LN "
                 "kernels (the manual bf16 update runs them)")
 
+    def _twin_fwd(self, x, x2, which: str, path: str):
+        """The twin Q heads on ``[x || x2]`` on a GPU ``path``, with the
+        local or the target weight stacks, or the frozen ones (the local
+        weights, taking no gradient).  fp32 hands both inputs to
+        twin_mlp_forward (torch.cat, or with DSAC_F32_CHAIN=1 the chain
+        kernel's loader); bf16 concatenates here."""
+        stacks = {"local": self._twin_local, "target": self._twin_target,
+                  "frozen": self._twin_local_frozen}[which]
+        if path == "fp32":
+            return Fops.twin_mlp_forward(x, *stacks, x2=x2)
+        return Fops.twin_mlp_forward_bf16(
+            torch.cat([x, x2], dim=-1), *stacks,
+            self._target_chain.ws16 if which == "target"
+            else self._twin_local_bf16)
+
     def _critic_q(self, states, actions):
-        if self._use_fused(states):
+        path = self._update_path(states)
+        if path != "torch":
             self._ln_no_twin_kernels()
-            if self._bf16:
-                x = torch.cat([states, actions], dim=-1)
-                return Fops.twin_mlp_forward_bf16(x, *self._twin_local,
-                                                  self._twin_local_bf16)
-            # x2: concatenated by torch.cat, or, with DSAC_F32_CHAIN=1, in
-            # the chain kernel's loader
-            return Fops.twin_mlp_forward(states, *self._twin_local,
-                                         x2=actions)
+            return self._twin_fwd(states, actions, "local", path)
         if self.variant in ("sac", "vsac"):
             return (self.local_critic_1(states, actions),
                     self.local_critic_2(states, actions))
         return self.local_critic(states, actions)
 
     def _target_q(self, states, actions):
-        if self._use_fused(states):
+        path = self._update_path(states)
+        if path != "torch":
             self._ln_no_twin_kernels()
-            if self._bf16:
-                x = torch.cat([states, actions], dim=-1)
-                return Fops.twin_mlp_forward_bf16(x, *self._twin_target,
-                                                  self._target_chain.ws16)
-            return Fops.twin_mlp_forward(states, *self._twin_target,
-                                         x2=actions)
+            return self._twin_fwd(states, actions, "target", path)
         if self.variant in ("sac", "vsac"):
             return (self.target_critic_1(states, actions),
                     self.target_critic_2(states, actions))
@@ -501,113 +556,7 @@ class SACEngine:
             return Fops.gather_log_alpha(one_hots, self.log_alpha).exp().detach()
         return self.log_alpha.exp().detach()
 
-    # -- prioritized replay ----------------------------------------------
-    def _per_unsupported(self) -> None:
-        """Raise for the combinations prioritized replay does not cover."""
-        why = None
-        if self.variant == "care":
-            why = "CAREEngine has no prioritized-replay path"
-        elif self.ddp is not None and getattr(self.ddp, "enabled", True):
-            why = "not supported with a data-parallel group attached"
-        elif self.degenerate_w and self.use_weighted_loss:
-            why = "not defined for weighted_loss_mode='reference'"
-        elif self.device.type == "cuda" and self._use_fused(
-                self.log_alpha) and not (
-                self._bf16
-                and os.environ.get("DSAC_NO_MANUAL", "0") != "1"):
-            why = ("on a GPU only the bf16 manual-backward path carries "
-                   "importance-sampling weights (not the fp32 fused path)")
-        if why is not None:
-            raise NotImplementedError(f"prioritized replay: {why}")
-
-    # -- truncated quantile critics ----------------------------------------
-    def _tqc_unsupported(self) -> None:
-        """Raise for the combinations truncated quantile critics do not
-        cover (checked at construction and again per update, where the
-        batch and the environment switches are known)."""
-        if not self.tqc_M:
-            return
-        from ..ops import has_native, native_enabled
-        why = None
-        if self.variant == "care":
-            why = "CAREEngine has no quantile-critic path"
-        elif self._per is not None:
-            why = "not supported together with prioritized replay"
-        elif self.degenerate_w and self.use_weighted_loss:
-            why = "not defined for weighted_loss_mode='reference'"
-        elif self.device.type == "cuda" and native_enabled() \
-                and has_native() and not (
-                self.precision == "bf16"
-                and os.environ.get("DSAC_NO_MANUAL", "0") != "1"):
-            why = ("on a GPU only the bf16 manual-backward path has the "
-                   "quantile loss kernels (not the fp32 path, not "
-                   "DSAC_NO_MANUAL=1)")
-        if why is not None:
-            raise NotImplementedError(f"truncated quantile critics: {why}")
-
-    # -- LayerNorm critics -------------------------------------------------
-    def _ln_unsupported(self, B: Optional[int] = None) -> None:
-        """Raise for the combinations LayerNorm critics do not cover
-        (checked at construction and again per update, where the batch and
-        the environment switches are known)."""
-        if not self.critic_ln:
-            return
-        from ..ops import has_native, native_enabled
-        gpu = self.device.type == "cuda" and native_enabled() \
-            and has_native()
-        why = None
-        if self.variant == "care":
-            why = "CAREEngine has no LayerNorm critic path"
-        elif gpu and self.precision != "bf16":
-            why = ("on a GPU only the bf16 manual-backward path has the LN "
-                   "chain kernels (not the fp32 GPU path)")
-        elif gpu and os.environ.get("DSAC_NO_MANUAL", "0") == "1":
-            why = ("the autograd bf16 path (DSAC_NO_MANUAL=1) has no LN "
-                   "chain kernels")
-        elif gpu and self.pcgrad and B is not None \
-                and (B // self.num_tasks) % 16:
-            why = (f"with pcgrad on a GPU each task's share of the batch "
-                   f"({B} / {self.num_tasks} rows) must be a multiple of "
-                   "the chain kernels' 16-row tile")
-        if why is not None:
-            raise NotImplementedError(f"critic_layer_norm: {why}")
-
     # -- PCGrad ------------------------------------------------------------
-    def _pcgrad_unsupported(self, B: Optional[int] = None) -> None:
-        """Raise for the combinations PCGrad does not cover (checked at
-        construction and again per update, where the batch, the attached
-        group and the environment switches are known)."""
-        if not self.pcgrad:
-            return
-        from ..ops import has_native, native_enabled
-        T = self.num_tasks
-        gpu = self.device.type == "cuda" and native_enabled() \
-            and has_native()
-        why = None
-        if self.variant == "care":
-            why = "CAREEngine has no per-task gradient arena"
-        elif not 2 <= T <= torch_ref.PCGRAD_MAX_T:
-            why = (f"num_tasks must be in 2..{torch_ref.PCGRAD_MAX_T} "
-                   f"(variant mtsac), got {T}")
-        elif self.ddp is not None and getattr(self.ddp, "enabled", True):
-            why = ("not supported with a data-parallel group attached (the "
-                   "[T, numel] arena would need the all-reduce)")
-        elif self.degenerate_w and self.use_weighted_loss:
-            why = "not defined for weighted_loss_mode='reference'"
-        elif gpu and self.precision != "bf16":
-            why = ("on a GPU only the bf16 manual-backward path writes "
-                   "per-task gradients (not the fp32 GPU path)")
-        elif gpu and os.environ.get("DSAC_NO_MANUAL", "0") == "1":
-            why = "the autograd bf16 path (DSAC_NO_MANUAL=1) has no arena"
-        elif gpu and os.environ.get("DSAC_KRNG", "1") != "1":
-            why = ("the visiting orders come from the device counter RNG "
-                   "(DSAC_KRNG=0 turns it off)")
-        elif B is not None and B % T:
-            why = (f"the batch ({B} rows) must divide into num_tasks = {T} "
-                   "equal parts (B % T != 0)")
-        if why is not None:
-            raise NotImplementedError(f"pcgrad: {why}")
-
     def _pcgrad_cpu(self, name: str, rows: torch.Tensor, states, group):
         """The torch path of one group: ``rows [B]`` are the per-row terms
         whose sum is the group's loss.  Forms the T per-task gradients with
@@ -674,6 +623,7 @@ class SACEngine:
                                      self.log_alpha.exp().detach()) / B
         return states.new_full((B,), 1.0 / B)
 
+    # -- prioritized replay ----------------------------------------------
     def attach_per(self, replay) -> None:
         """Pair with a ``sampling="prioritized"`` replay: its per_alpha /
         per_eps shape the new priorities, and every update of a batch that
@@ -733,12 +683,7 @@ class SACEngine:
         per = "is_weights" in batch
         if per:
             self._per_unsupported()
-        if self.tqc_M:
-            if per:
-                raise NotImplementedError(
-                    "truncated quantile critics: not supported together "
-                    "with prioritized replay")
-            self._tqc_unsupported()
+        self._tqc_unsupported(per)
         self._pcgrad_unsupported(batch["states"].shape[0])
         self._ln_unsupported(batch["states"].shape[0])
         out = self._update_tensors(batch)
@@ -747,13 +692,16 @@ class SACEngine:
         return out
 
     def _update_tensors(self, batch):
-        if self._use_fused(batch["states"]):
-            if self.degenerate_w and self.use_weighted_loss:
-                raise RuntimeError(
-                    "weighted_loss_mode='reference' (degenerate broadcast) "
-                    "is a CPU strict-parity mode; the fused HIP kernels "
-                    "implement corrected weighting (docs/PARITY.md)")
-            return self._update_tensors_fused(batch)
+        """Both engines' dispatch on the update path of the batch."""
+        path = self._update_path(batch["states"])
+        if path == "torch":
+            return self._update_tensors_torch(batch)
+        self._ref_weighting_is_cpu_only()
+        if path == "bf16-manual":
+            return self._update_tensors_manual(batch)
+        return self._update_tensors_fused(batch, path)
+
+    def _update_tensors_torch(self, batch):
         states = batch["states"]
         actions = batch["actions"]
         rewards = batch["rewards"]
@@ -1230,7 +1178,7 @@ class SACEngine:
         if not self._fuse_tail:
             flat_polyak_(*self._polyak_args())
 
-    def _update_tensors_fused(self, batch):
+    def _update_tensors_fused(self, batch, path: str):
         """GPU path: same math/order as update_tensors, restructured for
         the hardware (numerically identical):
 
@@ -1253,9 +1201,6 @@ class SACEngine:
         B = states.shape[0]
         A = self.cfg.action_dim
 
-        if self._bf16 \
-                and os.environ.get("DSAC_NO_MANUAL", "0") != "1":
-            return self._update_tensors_manual(batch)
         self.zero_grad()
 
         # --- batched actor forward: [next | current] halves (both use
@@ -1265,7 +1210,7 @@ class SACEngine:
         # profiles/r04_NOTES.md), so the TD block stays on the main stream.
         x_cat = torch.cat([next_states, states], dim=0)
         ws, bs = self._actor_weights()
-        if self._bf16:
+        if path == "bf16-autograd":
             out = Fops.mlp_forward_bf16(x_cat, ws, bs, self._actor_ws_bf16,
                                         grad_row_start=B)
         else:
@@ -1294,15 +1239,7 @@ class SACEngine:
         self.refresh_bf16("critic")
 
         # --- actor/alpha step (post-critic-step critic, frozen heads) --
-        if self._bf16:
-            xa = torch.cat([states, sampled_actions], dim=-1)
-            aq1, aq2 = Fops.twin_mlp_forward_bf16(xa,
-                                                  *self._twin_local_frozen,
-                                                  self._twin_local_bf16)
-        else:
-            aq1, aq2 = Fops.twin_mlp_forward(states,
-                                             *self._twin_local_frozen,
-                                             x2=sampled_actions)
+        aq1, aq2 = self._twin_fwd(states, sampled_actions, "frozen", path)
         policy_loss, loss_log_alpha, entropy = Fops.actor_alpha_loss(
             aq1, aq2, log_probs, log_stds, states, self.log_alpha, T, use_w,
             self.H_bar_f)
